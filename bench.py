@@ -20,6 +20,12 @@ asserts WORLD_SIZE == --gpus, so a scaling point can never silently be a 1-GPU
 number.  ``--device cpu`` (gloo) is the debug mode the CPU tests use.
 Gradients are accumulated and reduce-scattered in fp32 (Fleet ``main_grad``);
 ``--bf16-grads`` restores the round-1 bf16 gradient buffer.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints one JSON line.
+``--dump-outputs DIR`` also writes what the last timed step left behind (loss,
+parameters, optimizer state; sampled at fixed seeded positions) as ``DIR/*.npy``:
+the inputs are seeded, so two builds can be compared output for output.
+``--full`` is where secondary measurements belong; there are none today.
 """
 from __future__ import annotations
 
@@ -61,6 +67,31 @@ def _self_launch(args, argv) -> int:
     return subprocess.call(cmd, env=env)
 
 
+DUMP_SAMPLE = 1 << 20  # elements kept of each flat buffer: 4 MiB per array as float32
+
+
+def _dump_outputs(out_dir, loss, opt):
+    """What a caller of the timed step holds after the last step: its loss, the
+    updated parameters and the optimizer state (rank 0's shard).  Buffers longer
+    than DUMP_SAMPLE are sampled at fixed seeded positions, so two builds run with
+    the same arguments write arrays that compare element for element."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    sd = opt.state_dict()  # syncs the overlapped update first
+    bufs = {"loss": loss.reshape(1), "params": opt.flat_param,
+            "master": sd["master"], "adam_m": sd["m"], "adam_v": sd["v"]}
+    for name, t in bufs.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(2024)
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+    log(f"[bench] outputs written to {out_dir}: {', '.join(sorted(bufs))}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -87,6 +118,12 @@ def main():
                     help="tape: the framework's own reverse pass (torch autograd off); torch: torch.autograd")
     ap.add_argument("--dtype", default=None, choices=["bfloat16", "float32"],
                     help="debug only (CPU tests): override the model dtype; GPU results must stay bf16")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed (loss, a fixed seeded "
+                         "sample of the parameters and optimizer state) as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement; this benchmark has none, a plain run "
+                         "already does only what the headline figure needs")
     argv = sys.argv[1:]
     args = ap.parse_args(argv)
 
@@ -217,6 +254,10 @@ def main():
     ms = el / args.steps * 1000
     fpt = llama_flops_per_token(cfg, S)
     mfu = tps / world * fpt / 2.5e15
+    if args.dump_outputs:
+        opt.sync_params()  # may complete deferred all-gathers: a collective, so on every rank
+        if rank == 0:
+            _dump_outputs(args.dump_outputs, l.detach().float() * args.accum, opt)
     if rank == 0:
         log(f"[bench] final loss={final_loss:.4f} tokens/s={tps:.0f} per-gpu={tps/world:.0f} "
             f"ms/step={ms:.1f} MFU(2.5PF bf16 dense)={mfu*100:.1f}% peak_mem={peak():.1f}GiB")

@@ -124,22 +124,110 @@ __global__ void embedding_fwd_kernel(const long* __restrict__ ids, const T* __re
   }
 }
 
-// dW (fp32 accumulator) += scatter(dout).  One wave per token row: each lane adds
-// 4 contiguous floats -> a wave instruction covers 256 contiguous bytes, the
-// shape that runs at the full float-atomic rate (MI355X_MICROARCH Global float atomics).
-template <typename T>
-__global__ void embedding_bwd_kernel(const long* __restrict__ ids, const T* __restrict__ dout,
-                                     float* __restrict__ dW, long N, int H, long padding_idx) {
-  const int lane = threadIdx.x & 63;
-  const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
-  for (long r = wave; r < N; r += nwaves) {
-    const long id = ids[r];
-    if (id == padding_idx) continue;
-    for (int c = lane * 4; c < H; c += 256) {
+// dW (fp32 accumulator) += scatter(dout) over the token rows [r0, r1), without float
+// atomics: the same bits every run.  One 16-wave block per token row.  The block of the
+// FIRST row of the range that carries an id owns that id: it sums the range's rows with
+// this id in ascending row order in registers, its waves sharing the columns, and adds the
+// sum to dW with a plain read-modify-write (no other block of the launch touches that dW
+// row); the blocks of later duplicates leave.  Each lane adds 4 contiguous floats (VEC:
+// one 8- / 16-B access; needs H % 4 == 0 and 16-B aligned pointers).  The id scans are
+// wave-wide 512-B loads of a cache-resident array, (r1 - r0)^2 / 64 of them per launch: the
+// launcher walks long inputs in ranges of EMB_BWD_ROWS rows (launches of one stream run in
+// order, which keeps the summation order fixed across ranges too).
+// Measured against the float-atomic kernel it replaces (16384 rows, H 4096, bf16 dout,
+// 32000 ids, MI355X): uniform ids 377 vs 844 us, Zipf(1) ids (most frequent id on 1490
+// rows) 584 vs 1128 us; the serial sum of one dominant id costs more: 30 % of the rows on
+// one id 2.38 vs 1.45 ms, all rows on one id 5.77 vs 2.75 ms.
+constexpr long EMB_BWD_ROWS = 8192;
+constexpr int EMB_BWD_WAVES = 16;
+constexpr int EMB_BWD_U = 16;
+
+__device__ __forceinline__ void ld4(const u16* p, float* v) {
+  const u16x4 t = *reinterpret_cast<const u16x4*>(p);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = bf2f(t[j]);
+}
+__device__ __forceinline__ void ld4(const float* p, float* v) {
+  const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = t[j];
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(64 * EMB_BWD_WAVES) void embedding_bwd_kernel(const long* __restrict__ ids, const T* __restrict__ dout,
+                                     float* __restrict__ dW, long r0, long r1, int H, long padding_idx) {
+  __shared__ unsigned long long match[EMB_BWD_ROWS / 64];  // bit i of word c: row r + 64c + i has this id
+  __shared__ int off[EMB_BWD_ROWS / 64 + 1];               // matches before chunk c
+  __shared__ u16 rows[EMB_BWD_ROWS];                       // the matching rows (minus r), ascending
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long r = r0 + blockIdx.x;  // r, id: block-uniform
+  const long id = ids[r];
+  if (id == padding_idx) return;
+  // an earlier row of the range with this id?  64-row chunks of [r0, r), round-robin over the waves
+  bool hit = false;
+  for (long b = r0 + 64 * w; b < r; b += 64 * EMB_BWD_WAVES) {
+    const long q = b + lane;
+    hit |= q < r && ids[q] == id;
+  }
+  if (__syncthreads_or(hit)) return;
+  // the rows of [r, r1) with this id, found once by the whole block and compacted in order
+  const int nch = (int)((r1 - r + 63) / 64);
+  for (int c = w; c < nch; c += EMB_BWD_WAVES) {
+    const long q = r + 64L * c + lane;
+    const unsigned long long m = __ballot(q < r1 && ids[q] == id);
+    if (lane == 0) match[c] = m;
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c <= nch; c += blockDim.x) {
+    int n = 0;
+    for (int i = 0; i < c; ++i) n += __popcll(match[i]);
+    off[c] = n;
+  }
+  __syncthreads();
+  for (int c = w; c < nch; c += EMB_BWD_WAVES) {
+    const unsigned long long m = match[c];
+    if ((m >> lane) & 1) rows[off[c] + __popcll(m & ((1ULL << lane) - 1))] = (u16)(64 * c + lane);
+  }
+  __syncthreads();
+  const int nrows = off[nch];
+  float* dst = dW + id * H;
+  // a pass covers EMB_BWD_WAVES x 256 = 4096 columns, wave w the w-th 256 of them.  The
+  // loads of EMB_BWD_U rows are issued before they are added (in row order), so a
+  // frequent id costs one memory latency per EMB_BWD_U rows; dW is read and written once.
+  for (int c0 = 0; c0 < H; c0 += 256 * EMB_BWD_WAVES) {
+    const int col = c0 + w * 256 + lane * 4;
+    if (col >= H) continue;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int g = 0; g < nrows; g += EMB_BWD_U) {
+      float v[EMB_BWD_U][4];
+#pragma unroll
+      for (int u = 0; u < EMB_BWD_U; ++u) {
+        const bool on = g + u < nrows;
+        const T* src = dout + (r + rows[on ? g + u : 0]) * H + col;
+        if (VEC) {
+          if (on) ld4(src, v[u]);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[u][j] = (on && col + j < H) ? IO<T>::ld(src, j) : 0.f;
+        }
+        if (VEC && !on)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[u][j] = 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < EMB_BWD_U; ++u)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] += v[u][j];
+    }
+    if (VEC) {
+      f32x4 t = *reinterpret_cast<f32x4*>(dst + col);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t[j] += acc[j];
+      *reinterpret_cast<f32x4*>(dst + col) = t;
+    } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        if (c + j < H) atomicAdd(&dW[id * H + c + j], IO<T>::ld(dout, r * H + c + j));
+        if (col + j < H) dst[col + j] += acc[j];
     }
   }
 }
@@ -207,13 +295,16 @@ PA_EXPORT int pa_embedding_fwd(int dtype, const long* ids, const void* W, void* 
 
 PA_EXPORT int pa_embedding_bwd(int dtype, const long* ids, const void* dout, float* dW, long N,
                                int H, long padding_idx, hipStream_t st) {
-  long g = (N + 3) / 4;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  if (dtype == 1)
-    hipLaunchKernelGGL(embedding_bwd_kernel<u16>, dim3(g), dim3(256), 0, st, ids, (const u16*)dout, dW, N, H, padding_idx);
-  else
-    hipLaunchKernelGGL(embedding_bwd_kernel<float>, dim3(g), dim3(256), 0, st, ids, (const float*)dout, dW, N, H, padding_idx);
+  const bool vec = H % 4 == 0 && ((uintptr_t)dout | (uintptr_t)dW) % 16 == 0;
+  for (long r0 = 0; r0 < N; r0 += EMB_BWD_ROWS) {
+    const long r1 = r0 + EMB_BWD_ROWS < N ? r0 + EMB_BWD_ROWS : N;
+    const dim3 g(r1 - r0), b(64 * EMB_BWD_WAVES);  // one block per row
+#define PA_EB(T, VEC_) \
+  hipLaunchKernelGGL((embedding_bwd_kernel<T, VEC_>), g, b, 0, st, ids, (const T*)dout, dW, r0, r1, H, padding_idx)
+    if (dtype == 1) { if (vec) PA_EB(u16, true); else PA_EB(u16, false); }
+    else { if (vec) PA_EB(float, true); else PA_EB(float, false); }
+#undef PA_EB
+  }
   PA_LAUNCH_CHECK();
 }
 

@@ -236,10 +236,12 @@ __global__ __launch_bounds__(256) void momentum_multi_kernel(const MomT* __restr
   }
 }
 
-// sum of squares (for global-norm clipping): out[0] += sum(x^2); 16-B vector loads,
-// one fp32 atomic per block.
+// sum of squares (for global-norm clipping): out[0] += sum(x^2); 16-B vector loads.
+// Every block stores its partial and a one-block pass adds the partials in a fixed
+// order (no float atomics): the same bits every run, so the clip coefficient that
+// scales every gradient is reproducible.
 template <typename T>
-__global__ __launch_bounds__(256) void sumsq_kernel(const T* __restrict__ x, long n, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void sumsq_kernel(const T* __restrict__ x, long n, float* __restrict__ part) {
   __shared__ float red[4];
   float s = 0.f;
   const long n8 = n / 8;
@@ -254,7 +256,16 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const T* __restrict__ x, lon
     s += v * v;
   }
   s = block_sum<256>(s, red);
-  if (threadIdx.x == 0) atomicAdd(out, s);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void sumsq_finish_kernel(const float* __restrict__ part, int nb,
+                                                           float* __restrict__ out) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < nb; i += 256) s += part[i];
+  s = block_sum<256>(s, red);
+  if (threadIdx.x == 0) out[0] += s;
 }
 
 }  // namespace pa
@@ -337,13 +348,18 @@ PA_EXPORT int pa_momentum_p(int gdtype, int pdtype, void* p, const void* g, floa
   PA_LAUNCH_CHECK();
 }
 
-PA_EXPORT int pa_sumsq(int dtype, const void* x, long n, float* out, hipStream_t st) {
+// part: scratch for the per-block partials, pa_sumsq_parts() floats
+PA_EXPORT int pa_sumsq_parts() { return stream_grid(1L << 40, 256); }
+
+PA_EXPORT int pa_sumsq(int dtype, const void* x, long n, float* out, float* part, hipStream_t st) {
   if (n == 0) return 0;
+  if (part == nullptr) return (int)hipErrorInvalidValue;
   const int grid = stream_grid((n + 7) / 8, 256);
   if (dtype == 1)
-    hipLaunchKernelGGL(sumsq_kernel<u16>, dim3(grid), dim3(256), 0, st, (const u16*)x, n, out);
+    hipLaunchKernelGGL(sumsq_kernel<u16>, dim3(grid), dim3(256), 0, st, (const u16*)x, n, part);
   else
-    hipLaunchKernelGGL(sumsq_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, n, out);
+    hipLaunchKernelGGL(sumsq_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, n, part);
+  hipLaunchKernelGGL(sumsq_finish_kernel, dim3(1), dim3(256), 0, st, part, grid, out);
   PA_LAUNCH_CHECK();
 }
 

@@ -59,7 +59,8 @@ _SIGS = {
     "pa_momentum": [_I, _P, _P, _P, _L, _F, _P, _F, _I, _F, _F, _P],
     "pa_bn_running_update": [_I, _P, _P, _P, _P, _I, _L, _F, _F, _P],
     "pa_momentum_p": [_I, _I, _P, _P, _P, _L, _F, _P, _F, _I, _F, _F, _P],
-    "pa_sumsq": [_I, _P, _L, _P, _P],
+    "pa_sumsq": [_I, _P, _L, _P, _P, _P],
+    "pa_sumsq_parts": [],
     "pa_sgemm_set_deterministic": [_I],
     "pa_gemm_epi": [_I, _P, _P, _P, _P, _L, _I, _I, _I, _L, _L, _L, _P, _P, _I, _I, _P],
     "pa_sgemm_get_deterministic": [],

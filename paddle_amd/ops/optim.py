@@ -163,11 +163,18 @@ class MomentumMulti:
 
 
 def sumsq(x, out=None):
-    """Sum of squares into a 1-element fp32 tensor (accumulates into ``out``)."""
+    """Sum of squares into a 1-element fp32 tensor (accumulates into ``out``).
+
+    The kernel's second pass adds into ``out`` with a plain read-modify-write: calls
+    that accumulate into one ``out`` must run on one stream (they do: the clip and
+    the sharded optimizers call this on the current stream), which also fixes the
+    order of the sum."""
     if out is None:
         out = torch.zeros(1, dtype=torch.float32, device=x.device)
     if x.is_cuda:
-        N.call("pa_sumsq", N.dt(x), N.ptr(x), x.numel(), N.ptr(out), N.stream())
+        # per-block partials, summed in a fixed order by the kernel's second pass
+        part = torch.empty(N.lib().pa_sumsq_parts(), dtype=torch.float32, device=x.device)
+        N.call("pa_sumsq", N.dt(x), N.ptr(x), x.numel(), N.ptr(out), N.ptr(part), N.stream())
     else:
         out += x.float().pow(2).sum()
     return out

@@ -45,6 +45,49 @@ def test_bench_self_launches_two_ranks_and_matches_one():
     assert two["config"]["autograd"] == "tape" and two["config"]["comm_backend"] == "gloo"
 
 
+def test_dump_outputs_repeatable_and_full_flag(tmp_path):
+    """--dump-outputs writes float32 .npy arrays of the last timed step; the seeded
+    inputs make two runs with the same arguments agree (fp32 on the CPU: exactly),
+    and --full changes nothing about the headline run."""
+    import numpy as np
+
+    a, _ = _bench("--gpus", "1", "--micro-batch", "2", "--dump-outputs", str(tmp_path / "a"))
+    b, _ = _bench("--gpus", "1", "--micro-batch", "2", "--dump-outputs", str(tmp_path / "b"), "--full")
+    assert a["steps"] == 3 and a["ms_per_step"] > 0
+    assert a["final_loss"] == b["final_loss"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["adam_m.npy", "adam_v.npy", "loss.npy", "master.npy", "params.npy"]
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float32 and np.isfinite(x).all()
+        np.testing.assert_array_equal(x, y)
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert abs(float(np.load(tmp_path / "a" / "loss.npy")[0]) - a["final_loss"]) < 1e-4
+    assert np.load(tmp_path / "a" / "adam_m.npy").any()  # the step did update the state
+    # --steps sets the number of timed steps: one step fewer leaves another state behind
+    c, _ = _bench("--gpus", "1", "--micro-batch", "2", "--steps", "2", "--dump-outputs", str(tmp_path / "c"))
+    assert c["steps"] == 2
+    assert not np.array_equal(np.load(tmp_path / "c" / "master.npy"), np.load(tmp_path / "a" / "master.npy"))
+
+
+def test_dump_outputs_two_ranks(tmp_path):
+    """With two ranks rank 0 writes its shard; every rank takes part in the parameter
+    sync before it (a collective on the gloo path), and two runs agree exactly."""
+    import numpy as np
+
+    for d in ("a", "b"):
+        out, _ = _bench("--gpus", "2", "--micro-batch", "2", "--dump-outputs", str(tmp_path / d))
+        assert out["n_gpus"] == 2
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["adam_m.npy", "adam_v.npy", "loss.npy", "master.npy", "params.npy"]
+    for n in names:
+        x = np.load(tmp_path / "a" / n)
+        assert x.dtype == np.float32 and np.isfinite(x).all()
+        np.testing.assert_array_equal(x, np.load(tmp_path / "b" / n))
+
+
 def _model():
     from paddle_amd.models.llama import LLAMA_CONFIGS, LlamaConfig, LlamaForCausalLM
 

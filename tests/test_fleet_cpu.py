@@ -386,9 +386,11 @@ def test_data_parallel_buckets_match_single():
 
 
 def test_launcher_runs_two_ranks(tmp_path):
+    import os
     import subprocess
     import sys
 
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     script = tmp_path / "w.py"
     script.write_text(
         "import os, torch, torch.distributed as dist\n"
@@ -400,7 +402,7 @@ def test_launcher_runs_two_ranks(tmp_path):
 
     rc = subprocess.call([sys.executable, "-m", "paddle_amd.distributed.launch", "--nproc_per_node", "2",
                           "--master_port", str(_free_port()), str(script)],
-                         cwd="/root/repo", timeout=120)
+                         cwd=root, timeout=120)
     assert rc == 0
     assert (tmp_path / "out0").read_text() == "3.0" and (tmp_path / "out1").read_text() == "3.0"
 

@@ -1,7 +1,8 @@
 """The v1 config parser's ModelConfig / TrainerConfig output
 (trainer_config_helpers/config_proto.py) against the reference's own expected
 outputs: python/paddle/trainer_config_helpers/tests/configs/protostr/*.protostr
-(text-format ModelConfig files, read as data).  Each config below builds the
+(text-format ModelConfig files, read as data; stored under
+tests/golden/v1_protostr).  Each config below builds the
 topology of the reference test config of the same name; the layer names, types,
 sizes, activations, inputs, parameter names / sizes / dims and input / output
 layer names must match.  Also: proto2 wire round trip of a whole TrainerConfig."""
@@ -12,7 +13,7 @@ import pytest
 import paddle_amd.trainer_config_helpers as tch
 from paddle_amd.trainer_config_helpers import config_proto as cp
 
-PROTOSTR = "/root/reference/python/paddle/trainer_config_helpers/tests/configs/protostr"
+PROTOSTR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "v1_protostr")
 
 
 def _fc():
@@ -487,8 +488,6 @@ def _core(mc):
 @pytest.mark.parametrize("name", sorted(CONFIGS))
 def test_model_config_matches_reference_protostr(name):
     path = os.path.join(PROTOSTR, name + ".protostr")
-    if not os.path.exists(path):
-        pytest.skip("reference protostr not present")
     c = tch.parse_config(CONFIGS[name])
     got = _core(c.model_config())
     text = open(path).read()
@@ -508,6 +507,29 @@ def test_model_config_matches_reference_protostr(name):
     mc = c.model_config()
     assert cp.decode("ModelConfig", cp.encode("ModelConfig", mc)) == cp.from_text("ModelConfig", cp.to_text(
         "ModelConfig", mc))
+
+
+def _census():
+    import importlib.util
+
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "v1_census.py")
+    spec = importlib.util.spec_from_file_location("v1_census", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.mark.parametrize("name", sorted(CONFIGS))
+def test_whole_message_equals_reference_protostr(name):
+    """The strict comparison of tools/v1_census.py on the configs built above: every
+    field of the whole ModelConfig / TrainerConfig (sub-configs of conv / pool / norm
+    inputs, evaluators, sub_models included), unknown fields reported, floats to 1e-6."""
+    text = open(os.path.join(PROTOSTR, name + ".protostr")).read()
+    whole = text.lstrip().startswith("model_config")
+    exp = cp.from_text("TrainerConfig" if whole else "ModelConfig", text, strict=True)
+    c = tch.parse_config(CONFIGS[name])
+    got = c.trainer_config() if whole else c.model_config()
+    assert _census()._diff(got, exp) == []
 
 
 def test_trainer_config_wire_round_trip_and_text():
