@@ -1,0 +1,183 @@
+"""Autoregressive text generation with a KV cache for the dense LM models.
+
+``GenerationMixin`` gives a model ``init_cache`` / ``prefill`` / ``decode_step`` /
+``generate``.  The model supplies two hooks:
+
+  ``_prefill_hidden(input_ids, cache)``  the existing layer code over the whole
+        (right-padded) prompt, which also fills the cache -> hidden states [B, S, H];
+  ``_decode_hidden(tokens, cache)``      one new token per row against the cache
+        -> hidden states [B, 1, H];
+
+plus ``_lm_logits(y)`` for the LM head.  Prefill reuses the training kernels (under the
+causal mask right padding cannot influence a valid position); a decode step runs
+``ops.kv_append`` + ``ops.decode_attention`` per layer (``csrc/kernels/attn_decode.hip``).
+
+Cache layout: see :mod:`paddle_amd.ops.decode`.  A row's first decoded token overwrites
+the first padding slot of a short prompt: positions are per row (``cache.lens``).
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+
+from .. import ops
+from ..ops import _native as N
+from ..ops import fused as F
+from ..ops import gemm as _G
+from ..ops.decode import KVCache
+
+
+@torch.no_grad()
+def prefill_qkv_attention(y, w, bias, cos, sin, Hq, Hk):
+    """QKV projection (+ rotary when ``cos`` is given) and causal attention over a whole
+    prompt y [B, S, H], on the kernels the training forward uses.  Returns
+    (packed, o): the packed, already-rotated q|k|v [B, S, (Hq+2Hk)*D] (what the cache
+    stores) and the attention output [B, S, Hq*D]."""
+    B, S, K = y.shape
+    W = w.shape[1]
+    nh = Hq + 2 * Hk
+    D = W // nh
+    scale = 1.0 / math.sqrt(D)
+    if cos is not None and bias is None and F._qkv_rope_fused_ok(y, w, cos, Hq, Hk):
+        # rotary in the projection GEMM's epilogue (as ops.qkv_rope_attention)
+        T = B * S
+        packed = torch.empty(T, W, dtype=y.dtype, device=y.device)
+        _G.gemm_epi(_G.EPI_ROPE, F._c(y.reshape(T, K)), F._weight_t(w, T), T, W, K, out=packed, cos=cos, sin=sin,
+                    rope_cols=(Hq + Hk) * D, rope_S=S)
+        packed = packed.view(B, S, W)
+    else:
+        qkv = F._c(ops.linear(y, w, bias))
+        if cos is None:
+            packed = qkv
+        elif qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128):
+            packed = torch.empty_like(qkv)
+            N.call("pa_rope", 1, 1, N.ptr(qkv), W, N.ptr(packed), W, N.ptr(cos), N.ptr(sin), None,
+                   B, S, nh, Hq + Hk, D, 0, N.stream())
+        else:
+            x = qkv.view(B, S, nh, D)
+            packed = torch.cat([F._rope_ref(x[:, :, :Hq + Hk], cos, sin), x[:, :, Hq + Hk:]], 2).view(B, S, W)
+    p4 = packed.view(B, S, nh, D)
+    q, k, v = p4[:, :, :Hq], p4[:, :, Hq:Hq + Hk], p4[:, :, Hq + Hk:]
+    if packed.is_cuda and packed.dtype == torch.bfloat16 and D in (64, 128):
+        o, _ = F._fa_fwd(q, k, v, True, scale)
+    else:
+        o = F._attn_ref(q, k, v, True, scale)
+    return packed, o.reshape(B, S, Hq * D)
+
+
+def sample_next(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, generator=None):
+    """Next token per row from logits [B, V] (fp32 math): greedy, or temperature /
+    top-k / top-p (nucleus) sampling with ``generator`` driving the draws."""
+    logits = logits.float()
+    if not do_sample:
+        return logits.argmax(-1)
+    if temperature != 1.0:
+        logits = logits / max(float(temperature), 1e-6)
+    V = logits.shape[-1]
+    if top_k and 0 < int(top_k) < V:
+        kth = logits.topk(int(top_k), -1).values[:, -1:]
+        logits = logits.masked_fill(logits < kth, float("-inf"))
+    if top_p < 1.0:
+        sl, si = logits.sort(-1, descending=True)
+        sp = torch.softmax(sl, -1)
+        # drop a token when the mass before it already reaches top_p (the first always stays)
+        drop = (sp.cumsum(-1) - sp) >= float(top_p)
+        sl = sl.masked_fill(drop, float("-inf"))
+        logits = torch.full_like(logits, float("-inf")).scatter(-1, si, sl)
+    probs = torch.softmax(logits, -1)
+    return torch.multinomial(probs, 1, generator=generator).squeeze(-1)
+
+
+class GenerationMixin:
+    """KV-cache inference for a causal LM (see the module docstring for the hooks)."""
+
+    def _check_generation_supported(self):
+        if getattr(self, "tp", None) is not None:
+            raise NotImplementedError("generate() with tensor parallelism is not implemented")
+
+    def _gen_device(self):
+        return next(self.parameters()).device
+
+    def init_cache(self, batch: int, max_len: int) -> KVCache:
+        """An empty cache for ``batch`` rows of up to ``max_len`` tokens each."""
+        self._check_generation_supported()
+        cfg = self.cfg
+        if max_len > cfg.max_position_embeddings:
+            raise ValueError(f"cache of {max_len} tokens exceeds max_position_embeddings "
+                             f"({cfg.max_position_embeddings})")
+        kvh = getattr(cfg, "kv_heads", cfg.num_attention_heads)
+        p = next(self.parameters())
+        return KVCache(cfg.num_hidden_layers, batch, max_len, kvh, cfg.head_dim, p.dtype, p.device)
+
+    @torch.no_grad()
+    def prefill(self, input_ids, cache: KVCache, prompt_lens=None):
+        """Run the right-padded prompt [B, S] through the model, fill ``cache`` and return
+        the logits [B, V] of each row's last valid position (``prompt_lens[b] - 1``;
+        default: every row has S tokens)."""
+        self._check_generation_supported()
+        B, S = input_ids.shape
+        lens = [S] * B if prompt_lens is None else [int(x) for x in (
+            prompt_lens.tolist() if torch.is_tensor(prompt_lens) else prompt_lens)]
+        if len(lens) != B or min(lens) < 1 or max(lens) > S:
+            raise ValueError(f"prompt_lens must be {B} values in [1, {S}], got {lens}")
+        cache.reset()
+        cache.check_room(S)
+        y = self._prefill_hidden(input_ids, cache)
+        cache.set_lens(lens)
+        H = y.shape[-1]
+        last = torch.tensor([b * S + n - 1 for b, n in enumerate(lens)], dtype=torch.long, device=y.device)
+        return self._lm_logits(ops.row_gather(y.reshape(B * S, H), last))
+
+    @torch.no_grad()
+    def decode_step(self, tokens, cache: KVCache):
+        """Feed one token per row (``tokens`` [B]) at each row's own position
+        ``cache.lens[b]``; returns the logits [B, V] for the next token and advances the
+        cache by one.  ``generate`` is a loop over this."""
+        self._check_generation_supported()
+        cache.check_room(1)
+        y = self._decode_hidden(tokens.reshape(-1, 1), cache)
+        cache.advance(1)
+        return self._lm_logits(y.reshape(y.shape[0], -1))
+
+    @torch.no_grad()
+    def generate(self, input_ids, max_new_tokens, prompt_lens=None, do_sample=False, temperature=1.0, top_k=0,
+                 top_p=1.0, eos_token_id=None, pad_token_id=0, seed=None):
+        """Generate ``max_new_tokens`` tokens after the right-padded prompts ``input_ids``
+        [B, S] (``prompt_lens``: valid length per row, default S).
+
+        Returns ``(tokens [B, max_new_tokens] int64, lengths [B])``.  A row that has
+        emitted ``eos_token_id`` keeps emitting ``pad_token_id``; ``lengths`` counts the
+        tokens up to and including EOS."""
+        self._check_generation_supported()
+        B, S = input_ids.shape
+        max_new_tokens = int(max_new_tokens)
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be at least 1")
+        if S + max_new_tokens > self.cfg.max_position_embeddings:
+            raise ValueError(f"prompt ({S}) + max_new_tokens ({max_new_tokens}) exceeds max_position_embeddings "
+                             f"({self.cfg.max_position_embeddings})")
+        dev = input_ids.device
+        gen = None
+        if do_sample:
+            gen = torch.Generator(device=dev)
+            if seed is not None:
+                gen.manual_seed(int(seed))
+            else:
+                gen.seed()
+        cache = self.init_cache(B, S + max_new_tokens)
+        out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=torch.long, device=dev)
+        lengths = torch.full((B,), max_new_tokens, dtype=torch.long, device=dev)
+        done = torch.zeros(B, dtype=torch.bool, device=dev)
+        logits = self.prefill(input_ids, cache, prompt_lens)
+        for step in range(max_new_tokens):
+            nxt = sample_next(logits, do_sample, temperature, top_k, top_p, gen)
+            nxt = torch.where(done, torch.full_like(nxt, int(pad_token_id)), nxt)
+            out[:, step] = nxt
+            if eos_token_id is not None:
+                hit = (nxt == int(eos_token_id)) & ~done
+                lengths = torch.where(hit, torch.full_like(lengths, step + 1), lengths)
+                done = done | hit
+            if step + 1 < max_new_tokens:
+                logits = self.decode_step(nxt, cache)
+        return out, lengths

@@ -23,6 +23,7 @@ import torch
 from .. import ops
 from ..autograd import tape as _tape
 from ..nn import Layer
+from .generation import GenerationMixin, prefill_qkv_attention
 from .llama import _dt, _param
 
 
@@ -120,6 +121,26 @@ class GPTDecoderLayer(Layer):
         m = self._row_linear(ops.linear_gelu(y2, self.fc1_w, self.fc1_b), self.fc2_w, self.fc2_b)
         return m, h2
 
+    def forward_cached(self, x, residual, cache, layer_idx, prefill):
+        """``forward`` for inference with a KV cache (no tensor parallelism): the whole
+        prompt through the training kernels with its k / v stored at position 0
+        (prefill), or x [B, 1, H], one token per row against the cache (decode)."""
+        eps = self.cfg.layer_norm_eps
+        if residual is None:
+            h = x
+            y = ops.layer_norm(x, self.ln1_w, self.ln1_b, eps)
+        else:
+            y, h = ops.layer_norm(x, self.ln1_w, self.ln1_b, eps, residual=residual)
+        if prefill:
+            packed, a = prefill_qkv_attention(y, self.qkv_w, self.qkv_b, None, None, self.nh, self.nh)
+            ops.kv_append(packed, cache, layer_idx, self.nh, self.nh)
+        else:
+            q = ops.kv_append(ops.linear(y, self.qkv_w, self.qkv_b), cache, layer_idx, self.nh, self.nh)
+            a = ops.decode_attention(q, cache, layer_idx).view(x.shape[0], 1, -1)
+        a = ops.linear(a, self.out_w, self.out_b)
+        y2, h2 = ops.layer_norm(a, self.ln2_w, self.ln2_b, eps, residual=h)
+        return ops.linear(ops.linear_gelu(y2, self.fc1_w, self.fc1_b), self.fc2_w, self.fc2_b), h2
+
 
 class GPTEmbeddings(Layer):
     def __init__(self, cfg: GPTConfig, device=None, tp=None):
@@ -145,7 +166,7 @@ class GPTEmbeddings(Layer):
         return ops.position_add(x, self.position_embeddings)
 
 
-class GPTForCausalLM(Layer):
+class GPTForCausalLM(Layer, GenerationMixin):
     def __init__(self, cfg: GPTConfig, device=None, tp=None):
         super().__init__("gpt")
         self.cfg, self.tp = cfg, _tp_on(tp)
@@ -182,6 +203,24 @@ class GPTForCausalLM(Layer):
         if labels is None:
             return logits
         return ops.softmax_cross_entropy(logits, labels, inplace_grad=True)
+
+    # ---- generation hooks (models/generation.py)
+    def _cached_hidden(self, x, cache, prefill):
+        residual = None
+        for i, layer in enumerate(self.layers):
+            x, residual = layer.forward_cached(x, residual, cache, i, prefill)
+        y, _ = ops.layer_norm(x, self.ln_f_w, self.ln_f_b, self.cfg.layer_norm_eps, residual=residual)
+        return y
+
+    def _prefill_hidden(self, input_ids, cache):
+        return self._cached_hidden(self.embeddings(input_ids), cache, True)
+
+    def _decode_hidden(self, tokens, cache):
+        # learned positions gathered at each row's own length
+        return self._cached_hidden(self.embeddings(tokens, position_ids=cache.lens.view(-1, 1)), cache, False)
+
+    def _lm_logits(self, y):
+        return ops.linear_t(y, self.embeddings.word_embeddings)
 
 
 def gpt_flops_per_token(cfg: GPTConfig, seq_len: int) -> float:

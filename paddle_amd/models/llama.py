@@ -27,6 +27,7 @@ import torch
 from .. import ops
 from ..autograd import tape as _tape
 from ..nn import Layer
+from .generation import GenerationMixin, prefill_qkv_attention
 
 
 @dataclass
@@ -167,8 +168,34 @@ class LlamaDecoderLayer(Layer):
             m = self.tp.reduce_from_region(m)
         return m, h2
 
+    def _mlp(self, y2):
+        if self.mlp_interleaved:
+            return ops.swiglu_mlp(y2, self.gate_up_proj, self.down_proj)
+        return ops.linear(ops.swiglu(ops.linear(y2, self.gate_up_proj)), self.down_proj)
 
-class LlamaForCausalLM(Layer):
+    def forward_cached(self, x, residual, cos, sin, cache, layer_idx, prefill):
+        """``forward`` for inference with a KV cache (no tensor parallelism).  Prefill: the
+        whole prompt through the training kernels, its rotated k / v stored at position
+        0.  Decode: x [B, 1, H], one token per row appended and rotated at the row's own
+        position, then split-KV attention over the cache."""
+        eps = self.cfg.rms_norm_eps
+        if residual is None:
+            h = x
+            y = ops.rms_norm(x, self.input_layernorm, eps)
+        else:
+            y, h = ops.rms_norm(x, self.input_layernorm, eps, residual=residual)
+        if prefill:
+            packed, a = prefill_qkv_attention(y, self.qkv_proj, None, cos, sin, self.nh, self.nkv)
+            ops.kv_append(packed, cache, layer_idx, self.nh, self.nkv)
+        else:
+            q = ops.kv_append(ops.linear(y, self.qkv_proj), cache, layer_idx, self.nh, self.nkv, cos, sin)
+            a = ops.decode_attention(q, cache, layer_idx).view(x.shape[0], 1, -1)
+        a = ops.linear(a, self.o_proj)
+        y2, h2 = ops.rms_norm(a, self.post_attention_layernorm, eps, residual=h)
+        return self._mlp(y2), h2
+
+
+class LlamaForCausalLM(Layer, GenerationMixin):
     """``tp``: optional ``distributed.fleet.TPGroup`` -- Megatron tensor parallelism:
     QKV / gate|up column-parallel, o / down row-parallel (one all-reduce each),
     vocab-parallel embedding, vocab-sharded LM head + parallel cross entropy."""
@@ -238,6 +265,24 @@ class LlamaForCausalLM(Layer):
 
     def forward(self, input_ids, labels=None):
         return self.logits_and_loss(self.hidden_states(input_ids), labels)
+
+    # ---- generation hooks (models/generation.py)
+    def _cached_hidden(self, input_ids, cache, prefill):
+        x = self.embed(input_ids)
+        residual = None
+        for i, layer in enumerate(self.layers):
+            x, residual = layer.forward_cached(x, residual, self.rope_cos, self.rope_sin, cache, i, prefill)
+        y, _ = ops.rms_norm(x, self.norm, self.cfg.rms_norm_eps, residual=residual)
+        return y
+
+    def _prefill_hidden(self, input_ids, cache):
+        return self._cached_hidden(input_ids, cache, True)
+
+    def _decode_hidden(self, tokens, cache):
+        return self._cached_hidden(tokens, cache, False)
+
+    def _lm_logits(self, y):
+        return self.logits_and_loss(y, None)
 
 
 def shard_llama_state_dict(full: dict, cfg: LlamaConfig, rank: int, world: int) -> dict:

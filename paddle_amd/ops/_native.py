@@ -66,6 +66,11 @@ _SIGS = {
     "pa_sgemm_get_deterministic": [],
     "pa_transpose2d": [_I, _P, _P, _I, _I, _L, _L, _I, _L, _L, _P],
     "pa_flash_attn_fwd": [_P, _P, _P, _P, _P, _LP, _I, _I, _I, _I, _I, _I, _F, _I, _P],
+    "pa_kv_append": [_P, _LP, _P, _P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
+    "pa_i32_add": [_P, _I, _I, _P],
+    "pa_attn_decode_ok": [_I, _I, _I, _I, _I, _I, _LP],
+    "pa_attn_decode_splits": [_I, _I, _I],
+    "pa_attn_decode": [_P, _LP, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
     "pa_fa_bwd_set_variant": [_I],
     "pa_fa_fwd_set_variant": [_I],
     "pa_fa_bwd_get_variant": [],

@@ -1,0 +1,197 @@
+"""KV-cache decode ops: the cache object, ``kv_append`` and ``decode_attention``.
+
+GPU bf16 tensors run the gfx950 kernels of ``csrc/kernels/attn_decode.hip``; CPU
+tensors, other dtypes and shapes the kernels do not cover run the plain-torch
+definitions below (the fp32 oracle of the GPU tests).  These are inference ops: they
+record nothing on the tape and run under ``torch.no_grad()``.
+
+Cache layout: per layer ``k`` / ``v`` ``[B, max_len, Hk, D]`` (token-major, the layout
+the packed QKV projection already has, so an append is a row copy), and one int32
+device tensor ``lens[B]`` shared by all layers: the number of valid tokens per row.
+Rows may have different lengths (right-padded prompts); nothing on the decode path
+reads ``lens`` back to the host.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+
+from . import _native as N
+from .fused import _attn_ref, _fa_strides, ctypes_long_array
+
+__all__ = ["KVCache", "kv_append", "decode_attention"]
+
+
+class KVCache:
+    """Per-layer key / value storage for incremental decoding.
+
+    ``lens`` (int32, device) holds each row's valid length; ``max_len`` and an upper
+    bound of ``lens`` live on the host, so an append past the end raises without a
+    device read.  One step is: ``kv_append`` + ``decode_attention`` per layer (both see
+    the same ``lens``), then one ``advance(T)``."""
+
+    def __init__(self, num_layers, batch, max_len, num_kv_heads, head_dim, dtype=torch.bfloat16, device=None):
+        self.num_layers, self.batch, self.max_len = int(num_layers), int(batch), int(max_len)
+        self.num_kv_heads, self.head_dim = int(num_kv_heads), int(head_dim)
+        self.dtype, self.device = dtype, torch.device(device if device is not None else "cpu")
+        shape = (self.batch, self.max_len, self.num_kv_heads, self.head_dim)
+        self.k = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in range(self.num_layers)]
+        self.v = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in range(self.num_layers)]
+        self.lens = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
+        self._bound = 0  # host-side upper bound of lens
+
+    @property
+    def bound(self) -> int:
+        return self._bound
+
+    def reset(self):
+        """Forget every cached token (the storage is kept)."""
+        self.lens.zero_()
+        self._bound = 0
+
+    def check_room(self, T: int):
+        if self._bound + int(T) > self.max_len:
+            raise ValueError(f"KV cache overflow: {self._bound} cached + {int(T)} new tokens > max_len {self.max_len}")
+
+    def advance(self, T: int = 1):
+        """lens += T for every row (in place, on the stream: no host read)."""
+        self.check_room(T)
+        if self.lens.is_cuda:
+            N.call("pa_i32_add", N.ptr(self.lens), self.batch, int(T), N.stream())
+        else:
+            self.lens += int(T)
+        self._bound += int(T)
+
+    def set_lens(self, lens):
+        """lens = the given per-row lengths (host list or tensor), e.g. the prompt lengths
+        after a right-padded prefill; the host bound becomes their maximum."""
+        host = [int(x) for x in (lens.tolist() if torch.is_tensor(lens) else lens)]
+        if len(host) != self.batch or min(host) < 0 or max(host) > self.max_len:
+            raise ValueError(f"set_lens: need {self.batch} lengths in [0, {self.max_len}], got {host}")
+        self.lens.copy_(torch.tensor(host, dtype=torch.int32))
+        self._bound = max(host)
+
+
+def _rope_at(x, cos, sin, positions):
+    """neox rotation of x [B, T, H, D] at table rows positions [B, T]:
+    [a|b] -> [a*c - b*s, b*c + a*s] (``fused._rope_ref`` at a position offset)."""
+    D = x.shape[-1]
+    c = cos[positions].unsqueeze(2)
+    s = sin[positions].unsqueeze(2)
+    a, b = x[..., : D // 2].float(), x[..., D // 2:].float()
+    return torch.cat([a * c - b * s, b * c + a * s], -1).to(x.dtype)
+
+
+def _kv_append_ref(q4, cache, layer, Hq, Hk, cos, sin):
+    B, T = q4.shape[:2]
+    pos = cache.lens.long()
+    positions = pos.unsqueeze(1) + torch.arange(T, device=q4.device)
+    q, k, v = q4[:, :, :Hq], q4[:, :, Hq:Hq + Hk], q4[:, :, Hq + Hk:]
+    if cos is not None:
+        q, k = _rope_at(q, cos, sin, positions), _rope_at(k, cos, sin, positions)
+    bidx = torch.arange(B, device=q4.device).unsqueeze(1).expand(B, T)
+    cache.k[layer][bidx, positions] = k.to(cache.dtype)
+    cache.v[layer][bidx, positions] = v.to(cache.dtype)
+    return q.contiguous()
+
+
+def _aligned16(t):
+    return t.data_ptr() % 16 == 0
+
+
+def _append_kernel_ok(q4, cache, cos, sin):
+    D = q4.shape[-1]
+    if not (q4.is_cuda and q4.dtype == torch.bfloat16 and cache.dtype == torch.bfloat16 and D % 16 == 0):
+        return False
+    if q4.stride(-1) != 1 or any(s % 8 for s in q4.stride()[:3]) or not _aligned16(q4):
+        return False
+    if cos is not None and not (cos.is_cuda and cos.dtype == torch.float32 and sin.dtype == torch.float32
+                                and cos.is_contiguous() and sin.is_contiguous() and cos.shape[-1] == D // 2
+                                and sin.shape == cos.shape):
+        return False
+    return True
+
+
+@torch.no_grad()
+def kv_append(qkv, cache: KVCache, layer: int, num_heads: int, num_kv_heads: int | None = None, cos=None, sin=None):
+    """Write the T new tokens of a packed projection ``qkv`` [B, T, (Hq+2Hk)*D] into
+    layer ``layer`` of ``cache`` at rows ``cache.lens[b] + t`` and return q [B, T, Hq, D].
+
+    With ``cos`` / ``sin`` (the fp32 tables of ``rope_tables``) q and k are rotated at
+    their true positions ``lens[b] + t``; v is always copied bit for bit.  ``lens`` is
+    not advanced: call ``cache.advance(T)`` once after the last layer.  Raises
+    ``ValueError`` when the host-side bound says the append would pass ``max_len`` (or
+    the rotary table)."""
+    Hq, Hk = int(num_heads), int(num_kv_heads or num_heads)
+    B, T, W = qkv.shape
+    D = W // (Hq + 2 * Hk)
+    if W != (Hq + 2 * Hk) * D or B != cache.batch or Hk != cache.num_kv_heads or D != cache.head_dim:
+        raise ValueError(f"kv_append: qkv {tuple(qkv.shape)} does not match the cache "
+                         f"(B={cache.batch}, Hk={cache.num_kv_heads}, D={cache.head_dim}) with {Hq} heads")
+    if (cos is None) != (sin is None):
+        raise ValueError("kv_append: cos and sin go together")
+    cache.check_room(T)
+    if cos is not None and cache.bound + T > cos.shape[0]:
+        raise ValueError(f"kv_append: position {cache.bound + T - 1} is beyond the rotary table ({cos.shape[0]} rows)")
+    if qkv.stride(-1) != 1:
+        qkv = qkv.contiguous()
+    q4 = qkv.unflatten(-1, (Hq + 2 * Hk, D))  # a view: the last dim has unit stride
+    if not _append_kernel_ok(q4, cache, cos, sin):
+        return _kv_append_ref(q4, cache, layer, Hq, Hk, cos, sin)
+    q = torch.empty(B, T, Hq, D, dtype=qkv.dtype, device=qkv.device)
+    N.call("pa_kv_append", N.ptr(q4), ctypes_long_array(_fa_strides(q4)), N.ptr(cache.lens), N.ptr(cos), N.ptr(sin),
+           int(cos.shape[0]) if cos is not None else 0, N.ptr(cache.k[layer]), N.ptr(cache.v[layer]), cache.max_len,
+           N.ptr(q), B, T, Hq, Hk, D, N.stream())
+    return q
+
+
+def _decode_attention_ref(q, k, v, kv_len, scale):
+    """fp32 attention of one query token per row over the first kv_len[b] cached keys
+    (``fused._attn_ref`` per row; a row with no key gives zeros)."""
+    outs = []
+    for b, n in enumerate(kv_len.tolist()):
+        if n <= 0:
+            outs.append(torch.zeros_like(q[b:b + 1]))
+        else:
+            outs.append(_attn_ref(q[b:b + 1], k[b:b + 1, :n], v[b:b + 1, :n], False, scale))
+    return torch.cat(outs, 0)
+
+
+def default_num_splits(batch: int, num_kv_heads: int, max_len: int) -> int:
+    """The split count the host picks from the launch shape alone (never from the
+    lengths): enough workgroups for two per compute unit, at least 256 keys per split."""
+    return int(N.lib().pa_attn_decode_splits(int(batch), int(num_kv_heads), int(max_len)))
+
+
+@torch.no_grad()
+def decode_attention(q, cache: KVCache, layer: int, scale: float | None = None, num_splits: int | None = None,
+                     kv_len=None):
+    """Attention of one new token per row, q [B, 1, Hq, D], over layer ``layer`` of the
+    cache.  Row b attends to its first ``kv_len[b]`` cached tokens; ``kv_len`` defaults
+    to ``cache.lens + 1`` -- the token ``kv_append`` has just written, before
+    ``cache.advance()``.  Returns o [B, 1, Hq, D].
+
+    On the GPU (bf16, D in {64, 128}, Hq/Hk in {1, 2, 4, 8}) the key axis is cut into
+    ``num_splits`` ranges that run as separate workgroups and are merged by a second
+    kernel; the result is bit-identical from run to run for a given ``num_splits``."""
+    B, Tq, Hq, D = q.shape
+    if Tq != 1 or B != cache.batch or D != cache.head_dim:
+        raise ValueError(f"decode_attention: q {tuple(q.shape)} does not match the cache")
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if kv_len is None:
+        kv_len = cache.lens + 1
+    k, v = cache.k[layer], cache.v[layer]
+    Hk, S_max = cache.num_kv_heads, cache.max_len
+    if q.is_cuda and q.dtype == torch.bfloat16 and cache.dtype == torch.bfloat16 and q.stride(-1) == 1 \
+            and _aligned16(q) and kv_len.is_cuda and kv_len.dtype == torch.int32 and kv_len.is_contiguous():
+        ns = default_num_splits(B, Hk, S_max) if num_splits is None else int(num_splits)
+        qst = ctypes_long_array([q.stride(0), q.stride(2)])
+        if N.lib().pa_attn_decode_ok(B, S_max, Hq, Hk, D, ns, qst):
+            o = torch.empty(B, 1, Hq, D, dtype=q.dtype, device=q.device)
+            ws = torch.empty(B * Hq * ns * (D + 2), dtype=torch.float32, device=q.device)
+            N.call("pa_attn_decode", N.ptr(q), qst, N.ptr(k), N.ptr(v), N.ptr(kv_len), N.ptr(o), N.ptr(ws),
+                   B, S_max, Hq, Hk, D, float(scale), ns, N.stream())
+            return o
+    return _decode_attention_ref(q, k, v, kv_len, float(scale))
