@@ -135,8 +135,13 @@ class GPTDecoderLayer(Layer):
             packed, a = prefill_qkv_attention(y, self.qkv_w, self.qkv_b, None, None, self.nh, self.nh)
             ops.kv_append(packed, cache, layer_idx, self.nh, self.nh)
         else:
-            q = ops.kv_append(ops.linear(y, self.qkv_w, self.qkv_b), cache, layer_idx, self.nh, self.nh)
+            # decode: M = B rows per product, weight-streaming kernels (ops/skinny.py)
+            q = ops.kv_append(ops.skinny_linear(y, self.qkv_w, self.qkv_b), cache, layer_idx, self.nh, self.nh)
             a = ops.decode_attention(q, cache, layer_idx).view(x.shape[0], 1, -1)
+            a = ops.skinny_linear(a, self.out_w, self.out_b)
+            y2, h2 = ops.layer_norm(a, self.ln2_w, self.ln2_b, eps, residual=h)
+            m = ops.skinny_linear(y2, self.fc1_w, self.fc1_b, act="gelu_tanh")
+            return ops.skinny_linear(m, self.fc2_w, self.fc2_b), h2
         a = ops.linear(a, self.out_w, self.out_b)
         y2, h2 = ops.layer_norm(a, self.ln2_w, self.ln2_b, eps, residual=h)
         return ops.linear(ops.linear_gelu(y2, self.fc1_w, self.fc1_b), self.fc2_w, self.fc2_b), h2
@@ -220,7 +225,7 @@ class GPTForCausalLM(Layer, GenerationMixin):
         return self._cached_hidden(self.embeddings(tokens, position_ids=cache.lens.view(-1, 1)), cache, False)
 
     def _lm_logits(self, y):
-        return ops.linear_t(y, self.embeddings.word_embeddings)
+        return ops.skinny_linear_t(y, self.embeddings.word_embeddings)
 
 
 def gpt_flops_per_token(cfg: GPTConfig, seq_len: int) -> float:

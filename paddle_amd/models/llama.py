@@ -188,8 +188,16 @@ class LlamaDecoderLayer(Layer):
             packed, a = prefill_qkv_attention(y, self.qkv_proj, None, cos, sin, self.nh, self.nkv)
             ops.kv_append(packed, cache, layer_idx, self.nh, self.nkv)
         else:
-            q = ops.kv_append(ops.linear(y, self.qkv_proj), cache, layer_idx, self.nh, self.nkv, cos, sin)
+            # decode: M = B rows per product, weight-streaming kernels (ops/skinny.py)
+            q = ops.kv_append(ops.skinny_linear(y, self.qkv_proj), cache, layer_idx, self.nh, self.nkv, cos, sin)
             a = ops.decode_attention(q, cache, layer_idx).view(x.shape[0], 1, -1)
+            a = ops.skinny_linear(a, self.o_proj)
+            y2, h2 = ops.rms_norm(a, self.post_attention_layernorm, eps, residual=h)
+            if self.mlp_interleaved:
+                hm = ops.skinny_linear(y2, self.gate_up_proj, act="swiglu_interleaved")
+            else:
+                hm = ops.swiglu(ops.skinny_linear(y2, self.gate_up_proj))
+            return ops.skinny_linear(hm, self.down_proj), h2
         a = ops.linear(a, self.o_proj)
         y2, h2 = ops.rms_norm(a, self.post_attention_layernorm, eps, residual=h)
         return self._mlp(y2), h2
@@ -282,7 +290,9 @@ class LlamaForCausalLM(Layer, GenerationMixin):
         return self._cached_hidden(tokens, cache, False)
 
     def _lm_logits(self, y):
-        return self.logits_and_loss(y, None)
+        if self.lm_head is not None:
+            return ops.skinny_linear(y, self.lm_head)
+        return ops.skinny_linear_t(y, self.embed_tokens)
 
 
 def shard_llama_state_dict(full: dict, cfg: LlamaConfig, rank: int, world: int) -> dict:

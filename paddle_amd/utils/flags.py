@@ -42,6 +42,7 @@ _DEFAULTS = {
     "direct_one_shot_bytes": 1 << 20,  # one-shot / two-shot all-reduce switch
     "direct_max_spins": 1 << 25,  # bounded signal-barrier spins before a peer is declared lost
     "defer_expert_wgrad": True,  # ops/grouped.py: experts' dW once per step over all micro-batches (ops/accum.py)
+    "skinny_gemm": True,  # ops/skinny.py: decode-step GEMMs (M <= 16) on the weight-streaming kernel; off = ops.linear / linear_t
     "fp8_wgrad": False,  # ops/grouped.py: fp8 expert dW (measured slower, profiles/r5_moe_fp8_wgrad_NEGATIVE.md)
 }
 
