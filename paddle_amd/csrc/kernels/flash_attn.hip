@@ -1613,6 +1613,16 @@ PA_EXPORT int pa_fa_fwd_set_variant(int v) {
   g_fa_fwd_variant = v;
   return 0;
 }
+PA_EXPORT int pa_fa_fwd_get_variant() { return g_fa_fwd_variant; }
+
+// What the last launch resolved to, for tests that must know which kernel ran (the
+// launchers fall back between variants by shape): forward = 10 * D + kernel (1 =
+// fa_fwd_kernel, 2 = fa_fwd_kernel2), backward = 10 * D + kernel (0 = fa_bwd_kernel,
+// 1 / 2 = fa_bwd_kernel2 / its probe, 3 / 4 = fa_bwd_kernel3 atomics / slabs, 5 =
+// fa_bwd_kernel5).  Each is set in the branch that launches.  Host state only.
+static int g_fa_fwd_last = 0, g_fa_bwd_last = 0;
+PA_EXPORT int pa_fa_fwd_last() { return g_fa_fwd_last; }
+PA_EXPORT int pa_fa_bwd_last() { return g_fa_bwd_last; }
 
 static bool fa_v5_ok(int Sq, int Sk, int D, int causal) {
   return g_fa_bwd_variant == 5 && D == 128 && causal && Sk % 128 == 0 && Sq % 32 == 0 && Sq > 0;
@@ -1641,15 +1651,19 @@ PA_EXPORT int pa_flash_attn_fwd(const void* q, const void* k, const void* v, voi
   dim3 grid(Hq, B, (Sq + 127) / 128);
   const bool v2ok = g_fa_fwd_variant == 2 && (long)Sk * strides[4] < (1L << 31) && (long)Sk * strides[7] < (1L << 31);
   if (D == 128 && v2ok) {
+    g_fa_fwd_last = 1282;
     if (causal) hipLaunchKernelGGL((fa_fwd_kernel2<128, true>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((fa_fwd_kernel2<128, false>), grid, dim3(256), 0, st, p);
   } else if (D == 128) {
+    g_fa_fwd_last = 1281;
     if (causal) hipLaunchKernelGGL((fa_fwd_kernel<128, true>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((fa_fwd_kernel<128, false>), grid, dim3(256), 0, st, p);
   } else if (D == 64) {
+    g_fa_fwd_last = 641;
     if (causal) hipLaunchKernelGGL((fa_fwd_kernel<64, true>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((fa_fwd_kernel<64, false>), grid, dim3(256), 0, st, p);
   } else if (D == 256) {
+    g_fa_fwd_last = 2561;
     if (causal) hipLaunchKernelGGL((fa_fwd_kernel<256, true>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((fa_fwd_kernel<256, false>), grid, dim3(256), 0, st, p);
   } else {
@@ -1686,7 +1700,8 @@ PA_EXPORT int pa_flash_attn_bwd(const void* q, const void* k, const void* v, con
   int variant = fits32 ? g_fa_bwd_variant : 0;
   if (variant == 5 && !(fa_v5_ok(Sq, Sk, D, causal) && dq_part != nullptr)) variant = 4;
   if (variant == 4 && (D != 128 || dq_part == nullptr || !causal)) variant = 1;
-  if (variant != 4 && dq_acc == nullptr) return (int)hipErrorInvalidValue;
+  // only the partial-slab variants can leave the slab reduce to the caller
+  if (variant < 4 && dq_acc == nullptr) return (int)hipErrorInvalidValue;
   const long rows = (long)B * Hq * Sq;
   const int lpr = D / 8;
   const long pre_threads = rows * lpr;
@@ -1699,6 +1714,7 @@ PA_EXPORT int pa_flash_attn_bwd(const void* q, const void* k, const void* v, con
   dim3 grid(Hq, B, (Sk + 127) / 128);
   if (variant == 5) {
     const int nkb = Sk / 128;
+    g_fa_bwd_last = 1285;
     hipLaunchKernelGGL(fa_bwd_kernel5<true>, dim3(Hq, B, nkb), dim3(256), 0, st, p);
     if (dq_acc == nullptr) {
       PA_LAUNCH_CHECK();
@@ -1710,6 +1726,7 @@ PA_EXPORT int pa_flash_attn_bwd(const void* q, const void* k, const void* v, con
   if (D == 128 && (variant == 3 || variant == 4)) {
     const int nkb = (Sk + 127) / 128;
     dim3 g3(Hq, B, nkb);
+    g_fa_bwd_last = 1280 + variant;
     if (variant == 4) {
       if (causal) hipLaunchKernelGGL((fa_bwd_kernel3<true, true>), g3, dim3(512), 0, st, p);
       else hipLaunchKernelGGL((fa_bwd_kernel3<false, true>), g3, dim3(512), 0, st, p);
@@ -1728,13 +1745,14 @@ PA_EXPORT int pa_flash_attn_bwd(const void* q, const void* k, const void* v, con
   }
 #define PA_FA_BWD_LAUNCH(DD, CC)                                                                    \
   switch (variant) {                                                                      \
-    case 0: hipLaunchKernelGGL((fa_bwd_kernel<DD, CC>), grid, dim3(256), 0, st, p); break;         \
-    case 2: hipLaunchKernelGGL((fa_bwd_kernel2<DD, CC, true>), grid, dim3(256), 0, st, p); break;  \
-    default: hipLaunchKernelGGL((fa_bwd_kernel2<DD, CC, false>), grid, dim3(256), 0, st, p); break; \
+    case 0: g_fa_bwd_last = 10 * DD; hipLaunchKernelGGL((fa_bwd_kernel<DD, CC>), grid, dim3(256), 0, st, p); break; \
+    case 2: g_fa_bwd_last = 10 * DD + 2; hipLaunchKernelGGL((fa_bwd_kernel2<DD, CC, true>), grid, dim3(256), 0, st, p); break; \
+    default: g_fa_bwd_last = 10 * DD + 1; hipLaunchKernelGGL((fa_bwd_kernel2<DD, CC, false>), grid, dim3(256), 0, st, p); break; \
   }
   if (D == 128) {
     if (causal) { PA_FA_BWD_LAUNCH(128, true) } else { PA_FA_BWD_LAUNCH(128, false) }
   } else if (D == 256) {
+    g_fa_bwd_last = 2560;
     if (causal) hipLaunchKernelGGL((fa_bwd_kernel<256, true>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((fa_bwd_kernel<256, false>), grid, dim3(256), 0, st, p);
   } else {

@@ -78,6 +78,9 @@ _SIGS = {
     "pa_fa_bwd_set_variant": [_I],
     "pa_fa_fwd_set_variant": [_I],
     "pa_fa_bwd_get_variant": [],
+    "pa_fa_fwd_last": [],
+    "pa_fa_fwd_get_variant": [],
+    "pa_fa_bwd_last": [],
     "pa_add_attn_fwd": [_P, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _P],
     "pa_add_attn_bwd": [_P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "pa_lstm_cell_fwd": [_P, _P, _P, _P, _P, _P, _L, _P, _L, _I, _I, _P],

@@ -18,7 +18,7 @@ import math
 import torch
 
 from . import _native as N
-from .fused import _attn_ref, _fa_strides, ctypes_long_array
+from .fused import _attn_ref, _check_scale, _fa_strides, ctypes_long_array
 
 __all__ = ["KVCache", "kv_append", "decode_attention"]
 
@@ -180,6 +180,7 @@ def decode_attention(q, cache: KVCache, layer: int, scale: float | None = None, 
         raise ValueError(f"decode_attention: q {tuple(q.shape)} does not match the cache")
     if scale is None:
         scale = 1.0 / math.sqrt(D)
+    _check_scale(scale, "decode_attention")
     if kv_len is None:
         kv_len = cache.lens + 1
     k, v = cache.k[layer], cache.v[layer]

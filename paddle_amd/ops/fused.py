@@ -286,12 +286,13 @@ def _fa_fwd(q, k, v, causal, scale, out=None):
     return o, lse
 
 
-def _fa_bwd(q, k, v, o, do, lse, causal, scale, dk, dv, dq_rope_out=None):
+def _fa_bwd(q, k, v, o, do, lse, causal, scale, dk, dv, dq_rope_out=None, dq_acc=None):
     """dk/dv: [B, Sk, Hq, D] views (expanded over q heads) written by the kernel.
 
-    Returns the fp32 dQ accumulator [B, Sq, Hq, D] -- or, with ``dq_rope_out =
-    (out, row_stride, cos, sin)`` on the partial-slab path, writes the
-    inverse-rotated bf16 dQ straight into ``out`` and returns None."""
+    Returns the fp32 dQ accumulator [B, Sq, Hq, D] (``dq_acc`` if the caller brings a
+    contiguous one) -- or, with ``dq_rope_out = (out, row_stride, cos, sin)`` on the
+    partial-slab path, writes the inverse-rotated bf16 dQ straight into ``out`` and
+    returns None."""
     B, Sq, Hq, D = q.shape
     Sk, Hk = k.shape[1], k.shape[2]
     delta = torch.empty(B, Hq, Sq, dtype=torch.float32, device=q.device)
@@ -305,7 +306,12 @@ def _fa_bwd(q, k, v, o, do, lse, causal, scale, dk, dv, dq_rope_out=None):
         # per-key-block dQ partial slabs (plain stores) summed by a reduce kernel
         part = torch.empty(nkb, B, Hq, Sq, D, dtype=torch.bfloat16, device=q.device)
     fused = part is not None and dq_rope_out is not None
-    dq_acc = None if fused else torch.empty(B, Sq, Hq, D, dtype=torch.float32, device=q.device)
+    if fused:
+        dq_acc = None
+    elif dq_acc is None:
+        dq_acc = torch.empty(B, Sq, Hq, D, dtype=torch.float32, device=q.device)
+    else:
+        assert dq_acc.shape == (B, Sq, Hq, D) and dq_acc.dtype == torch.float32 and dq_acc.is_contiguous()
     N.call("pa_flash_attn_bwd", N.ptr(q), N.ptr(k), N.ptr(v), N.ptr(o), N.ptr(do), N.ptr(lse),
            N.ptr(delta), N.ptr(dq_acc), N.ptr(dk), N.ptr(dv), st, B, Sq, Sk, Hq, Hk, D,
            float(scale), int(causal), N.ptr(part), N.stream())
@@ -344,6 +350,13 @@ def _fa_bwd_split(q, k, v, o, do, lse, causal, scale, dq, dk, dv, cos=None, sin=
            N.ptr(dq), N.ptr(dk), N.ptr(dv), st, B, Sq, Sk, Hq, Hk, D, float(scale), int(causal),
            N.ptr(cos), N.ptr(sin), N.stream())
     return True
+
+
+def _check_scale(scale, what):
+    # the kernels take the running max over raw scores and scale afterwards: that
+    # commutes with max only for a positive scale
+    if not scale > 0:
+        raise ValueError(f"{what}: softmax scale must be positive, got {scale}")
 
 
 def ctypes_long_array(vals):
@@ -385,6 +398,7 @@ def flash_attention(q, k, v, causal=True, scale=None):
     instantiated at D = 256 (register-spilling: a correctness path)."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    _check_scale(scale, "flash_attention")
     if q.is_cuda:
         if q.dtype != torch.bfloat16 or q.shape[-1] not in (64, 128, 256):
             raise NotImplementedError("flash_attention kernel: bf16 with head_dim 64/128/256")
@@ -451,6 +465,7 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal=True
         raise ValueError("cu_seqlens_q and cu_seqlens_k describe different batch sizes")
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    _check_scale(scale, "flash_attention_varlen")
     if q.is_cuda and q.dtype == torch.bfloat16 and q.shape[-1] in (64, 128, 256):
         return _tape.apply(_FlashAttnVarlenFn, q, k, v, cu_q, cu_k, causal, scale)
     outs = []
