@@ -12,8 +12,11 @@ plus ``_lm_logits(y)`` for the LM head.  Prefill reuses the training kernels (un
 causal mask right padding cannot influence a valid position); a decode step runs
 ``ops.kv_append`` + ``ops.decode_attention`` per layer (``csrc/kernels/attn_decode.hip``).
 
-Cache layout: see :mod:`paddle_amd.ops.decode`.  A row's first decoded token overwrites
-the first padding slot of a short prompt: positions are per row (``cache.lens``).
+Cache layout: see :mod:`paddle_amd.ops.decode` (one slab per layer, the default) and
+:mod:`paddle_amd.ops.paged` (blocks from a shared pool: ``init_cache(..., paged=True)``,
+``generate(..., cache="paged")``; ``prefill(..., rows=...)`` replaces single rows).  A
+row's first decoded token overwrites the first padding slot of a short prompt: positions
+are per row (``cache.lens``).
 """
 from __future__ import annotations
 
@@ -26,6 +29,7 @@ from ..ops import _native as N
 from ..ops import fused as F
 from ..ops import gemm as _G
 from ..ops.decode import KVCache
+from ..ops.paged import DEFAULT_BLOCK_SIZE, PagedKVCache
 
 
 @torch.no_grad()
@@ -99,8 +103,10 @@ class GenerationMixin:
     def _gen_device(self):
         return next(self.parameters()).device
 
-    def init_cache(self, batch: int, max_len: int) -> KVCache:
-        """An empty cache for ``batch`` rows of up to ``max_len`` tokens each."""
+    def init_cache(self, batch: int, max_len: int, paged: bool = False, block_size=None, num_blocks=None):
+        """An empty cache for ``batch`` rows of up to ``max_len`` tokens each: one slab per
+        layer, or with ``paged=True`` a pool of ``num_blocks`` blocks of ``block_size``
+        tokens (default: ``batch * ceil(max_len / block_size)``, the slab's capacity)."""
         self._check_generation_supported()
         cfg = self.cfg
         if max_len > cfg.max_position_embeddings:
@@ -108,29 +114,70 @@ class GenerationMixin:
                              f"({cfg.max_position_embeddings})")
         kvh = getattr(cfg, "kv_heads", cfg.num_attention_heads)
         p = next(self.parameters())
+        if paged:
+            return PagedKVCache(cfg.num_hidden_layers, batch, max_len, kvh, cfg.head_dim, p.dtype, p.device,
+                                block_size=block_size, num_blocks=num_blocks)
+        if block_size is not None or num_blocks is not None:
+            raise ValueError("init_cache: block_size / num_blocks need paged=True")
         return KVCache(cfg.num_hidden_layers, batch, max_len, kvh, cfg.head_dim, p.dtype, p.device)
 
     @torch.no_grad()
-    def prefill(self, input_ids, cache: KVCache, prompt_lens=None):
+    def prefill(self, input_ids, cache, prompt_lens=None, rows=None):
         """Run the right-padded prompt [B, S] through the model, fill ``cache`` and return
         the logits [B, V] of each row's last valid position (``prompt_lens[b] - 1``;
-        default: every row has S tokens)."""
+        default: every row has S tokens).
+
+        A paged cache reserves each row's own prompt length, not S: padding in the tail of
+        a row's last block is written (and overwritten by the row's next tokens), padding
+        beyond it is dropped.  With ``rows`` (paged only) ``input_ids`` is
+        ``[len(rows), S]``: those cache rows are freed, reserved and refilled and every
+        other row keeps its blocks, its length and its tokens; the logits are
+        ``[len(rows), V]``."""
         self._check_generation_supported()
         B, S = input_ids.shape
+        paged = getattr(cache, "paged", False)
+        if rows is not None and not paged:
+            raise ValueError("prefill: rows= needs a paged cache")
         lens = [S] * B if prompt_lens is None else [int(x) for x in (
             prompt_lens.tolist() if torch.is_tensor(prompt_lens) else prompt_lens)]
         if len(lens) != B or min(lens) < 1 or max(lens) > S:
             raise ValueError(f"prompt_lens must be {B} values in [1, {S}], got {lens}")
-        cache.reset()
-        cache.check_room(S)
-        y = self._prefill_hidden(input_ids, cache)
-        cache.set_lens(lens)
+        if paged:
+            y = self._prefill_paged(input_ids, cache, lens, rows)
+        else:
+            cache.reset()
+            cache.check_room(S)
+            y = self._prefill_hidden(input_ids, cache)
+            cache.set_lens(lens)
         H = y.shape[-1]
         last = torch.tensor([b * S + n - 1 for b, n in enumerate(lens)], dtype=torch.long, device=y.device)
         return self._lm_logits(ops.row_gather(y.reshape(B * S, H), last))
 
+    def _prefill_paged(self, input_ids, cache, lens, rows):
+        B, S = input_ids.shape
+        if S > cache.max_len:
+            raise ValueError(f"KV cache overflow: a prompt of {S} tokens > max_len {cache.max_len}")
+        if rows is None:
+            if B != cache.batch:
+                raise ValueError(f"prefill: {B} prompts for a cache of {cache.batch} rows")
+            cache.reset()
+        else:
+            rows = cache._check_rows(rows)
+            if len(rows) != B:
+                raise ValueError(f"prefill: {B} prompts for rows {rows}")
+            # the rows' own blocks come back first: raise now, with nothing freed, if even so the pool is short
+            bs = cache.block_size
+            if sum(-(-n // bs) - len(cache.row_blocks(r)) for r, n in zip(rows, lens)) > cache.blocks_free:
+                raise ValueError(f"paged KV cache: out of blocks for prompts of {lens} tokens in rows {rows}")
+            cache.free_rows(rows)
+        cache.reserve(lens, rows)
+        with cache.prefilling(rows):
+            y = self._prefill_hidden(input_ids, cache)
+        cache.set_lens(lens, rows)
+        return y
+
     @torch.no_grad()
-    def decode_step(self, tokens, cache: KVCache):
+    def decode_step(self, tokens, cache):
         """Feed one token per row (``tokens`` [B]) at each row's own position
         ``cache.lens[b]``; returns the logits [B, V] for the next token and advances the
         cache by one.  ``generate`` is a loop over this."""
@@ -142,14 +189,23 @@ class GenerationMixin:
 
     @torch.no_grad()
     def generate(self, input_ids, max_new_tokens, prompt_lens=None, do_sample=False, temperature=1.0, top_k=0,
-                 top_p=1.0, eos_token_id=None, pad_token_id=0, seed=None):
+                 top_p=1.0, eos_token_id=None, pad_token_id=0, seed=None, cache="contiguous", block_size=None):
         """Generate ``max_new_tokens`` tokens after the right-padded prompts ``input_ids``
         [B, S] (``prompt_lens``: valid length per row, default S).
 
         Returns ``(tokens [B, max_new_tokens] int64, lengths [B])``.  A row that has
         emitted ``eos_token_id`` keeps emitting ``pad_token_id``; ``lengths`` counts the
-        tokens up to and including EOS."""
+        tokens up to and including EOS.
+
+        ``cache="paged"`` keeps the keys and values in blocks of ``block_size`` tokens from
+        a pool of ``sum_b ceil((prompt_len_b + max_new_tokens) / block_size)`` blocks --
+        what the rows can reach, not ``B * (S + max_new_tokens)`` slots; the tokens are the
+        same."""
         self._check_generation_supported()
+        if cache not in ("contiguous", "paged"):
+            raise ValueError(f"generate: cache must be 'contiguous' or 'paged', got {cache!r}")
+        if block_size is not None and cache != "paged":
+            raise ValueError("generate: block_size needs cache='paged'")
         B, S = input_ids.shape
         max_new_tokens = int(max_new_tokens)
         if max_new_tokens < 1:
@@ -165,7 +221,14 @@ class GenerationMixin:
                 gen.manual_seed(int(seed))
             else:
                 gen.seed()
-        cache = self.init_cache(B, S + max_new_tokens)
+        if cache == "paged":
+            bs = DEFAULT_BLOCK_SIZE if block_size is None else int(block_size)
+            plens = [S] * B if prompt_lens is None else [int(x) for x in (
+                prompt_lens.tolist() if torch.is_tensor(prompt_lens) else prompt_lens)]
+            cache = self.init_cache(B, S + max_new_tokens, paged=True, block_size=bs,
+                                    num_blocks=sum(-(-(n + max_new_tokens) // bs) for n in plens))
+        else:
+            cache = self.init_cache(B, S + max_new_tokens)
         out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=torch.long, device=dev)
         lengths = torch.full((B,), max_new_tokens, dtype=torch.long, device=dev)
         done = torch.zeros(B, dtype=torch.bool, device=dev)

@@ -5,6 +5,6 @@ from .fused import (apply_rotary, embedding, flash_attention, flash_attention_va
                     deinterleave_gate_up, interleave_gate_up, qkv_rope_attention, swiglu_mlp, add, scale,
                     position_add, mean_valid, cross_entropy_tokens, reshape, stack_mean,
                     row_gather, concat_rows)
-from .decode import KVCache, kv_append, decode_attention  # noqa: F401
+from .decode import KVCache, PagedKVCache, kv_append, decode_attention  # noqa: F401
 from . import skinny  # noqa: F401
 from .skinny import skinny_ok, skinny_linear, skinny_linear_t, skinny_default_splits  # noqa: F401

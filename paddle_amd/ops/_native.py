@@ -71,6 +71,9 @@ _SIGS = {
     "pa_attn_decode_ok": [_I, _I, _I, _I, _I, _I, _LP],
     "pa_attn_decode_splits": [_I, _I, _I],
     "pa_attn_decode": [_P, _LP, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
+    "pa_kv_append_paged": [_P, _LP, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P],
+    "pa_attn_decode_paged_ok": [_I, _I, _I, _I, _I, _I, _LP, _I, _I, _I],
+    "pa_attn_decode_paged": [_P, _LP, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
     "pa_gemm_skinny_ok": [_I, _I, _I, _I, _L, _L, _L, _I, _I, _P, _P, _P, _P],
     "pa_gemm_skinny_splits": [_I, _I, _I],
     "pa_gemm_skinny_ws_floats": [_I, _I, _I],

@@ -10,6 +10,9 @@ the packed QKV projection already has, so an append is a row copy), and one int3
 device tensor ``lens[B]`` shared by all layers: the number of valid tokens per row.
 Rows may have different lengths (right-padded prompts); nothing on the decode path
 reads ``lens`` back to the host.
+
+``PagedKVCache`` (:mod:`paddle_amd.ops.paged`) stores the same tokens in fixed-size blocks
+from a shared pool; ``kv_append`` and ``decode_attention`` take either cache.
 """
 from __future__ import annotations
 
@@ -20,7 +23,7 @@ import torch
 from . import _native as N
 from .fused import _attn_ref, _check_scale, _fa_strides, ctypes_long_array
 
-__all__ = ["KVCache", "kv_append", "decode_attention"]
+__all__ = ["KVCache", "PagedKVCache", "kv_append", "decode_attention"]
 
 
 class KVCache:
@@ -114,7 +117,8 @@ def _append_kernel_ok(q4, cache, cos, sin):
 
 
 @torch.no_grad()
-def kv_append(qkv, cache: KVCache, layer: int, num_heads: int, num_kv_heads: int | None = None, cos=None, sin=None):
+def kv_append(qkv, cache, layer: int, num_heads: int, num_kv_heads: int | None = None, cos=None, sin=None,
+              rows=None):
     """Write the T new tokens of a packed projection ``qkv`` [B, T, (Hq+2Hk)*D] into
     layer ``layer`` of ``cache`` at rows ``cache.lens[b] + t`` and return q [B, T, Hq, D].
 
@@ -122,15 +126,24 @@ def kv_append(qkv, cache: KVCache, layer: int, num_heads: int, num_kv_heads: int
     their true positions ``lens[b] + t``; v is always copied bit for bit.  ``lens`` is
     not advanced: call ``cache.advance(T)`` once after the last layer.  Raises
     ``ValueError`` when the host-side bound says the append would pass ``max_len`` (or
-    the rotary table)."""
+    the rotary table).
+
+    ``rows`` (paged cache only): a host list that maps the input's batch rows onto cache
+    rows, so that ``qkv`` [len(rows), T, ...] fills a subset of the cache's rows."""
     Hq, Hk = int(num_heads), int(num_kv_heads or num_heads)
     B, T, W = qkv.shape
     D = W // (Hq + 2 * Hk)
-    if W != (Hq + 2 * Hk) * D or B != cache.batch or Hk != cache.num_kv_heads or D != cache.head_dim:
+    paged = getattr(cache, "paged", False)
+    if rows is not None and not paged:
+        raise ValueError("kv_append: rows= needs a paged cache (a contiguous cache appends to every row)")
+    if W != (Hq + 2 * Hk) * D or (B != cache.batch and not paged) or Hk != cache.num_kv_heads \
+            or D != cache.head_dim:
         raise ValueError(f"kv_append: qkv {tuple(qkv.shape)} does not match the cache "
                          f"(B={cache.batch}, Hk={cache.num_kv_heads}, D={cache.head_dim}) with {Hq} heads")
     if (cos is None) != (sin is None):
         raise ValueError("kv_append: cos and sin go together")
+    if paged:
+        return _paged.kv_append_paged(qkv, cache, layer, Hq, Hk, cos, sin, rows)
     cache.check_room(T)
     if cos is not None and cache.bound + T > cos.shape[0]:
         raise ValueError(f"kv_append: position {cache.bound + T - 1} is beyond the rotary table ({cos.shape[0]} rows)")
@@ -165,7 +178,7 @@ def default_num_splits(batch: int, num_kv_heads: int, max_len: int) -> int:
 
 
 @torch.no_grad()
-def decode_attention(q, cache: KVCache, layer: int, scale: float | None = None, num_splits: int | None = None,
+def decode_attention(q, cache, layer: int, scale: float | None = None, num_splits: int | None = None,
                      kv_len=None):
     """Attention of one new token per row, q [B, 1, Hq, D], over layer ``layer`` of the
     cache.  Row b attends to its first ``kv_len[b]`` cached tokens; ``kv_len`` defaults
@@ -183,6 +196,8 @@ def decode_attention(q, cache: KVCache, layer: int, scale: float | None = None, 
     _check_scale(scale, "decode_attention")
     if kv_len is None:
         kv_len = cache.lens + 1
+    if getattr(cache, "paged", False):
+        return _paged.decode_attention_paged(q, cache, layer, float(scale), num_splits, kv_len)
     k, v = cache.k[layer], cache.v[layer]
     Hk, S_max = cache.num_kv_heads, cache.max_len
     if q.is_cuda and q.dtype == torch.bfloat16 and cache.dtype == torch.bfloat16 and q.stride(-1) == 1 \
@@ -196,3 +211,7 @@ def decode_attention(q, cache: KVCache, layer: int, scale: float | None = None, 
                    B, S_max, Hq, Hk, D, float(scale), ns, N.stream())
             return o
     return _decode_attention_ref(q, k, v, kv_len, float(scale))
+
+
+from . import paged as _paged  # noqa: E402  (paged.py uses the helpers above)
+from .paged import PagedKVCache  # noqa: E402,F401
