@@ -17,6 +17,10 @@ Cache layout: see :mod:`paddle_amd.ops.decode` (one slab per layer, the default)
 ``generate(..., cache="paged")``; ``prefill(..., rows=...)`` replaces single rows).  A
 row's first decoded token overwrites the first padding slot of a short prompt: positions
 are per row (``cache.lens``).
+
+``quantize_weights()`` turns the decoder layers' matrices into ``ops.Fp8Weight``s (e4m3 codes,
+power-of-two column scales): decode steps run them on the fp8 weight-streaming kernel,
+prefill on an exact dequantised image (ops/skinny_fp8.py).
 """
 from __future__ import annotations
 
@@ -25,6 +29,7 @@ import math
 import torch
 
 from .. import ops
+from ..autograd import tape as _tape
 from ..ops import _native as N
 from ..ops import fused as F
 from ..ops import gemm as _G
@@ -93,8 +98,62 @@ def sample_next(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, ge
     return torch.multinomial(probs, 1, generator=generator).squeeze(-1)
 
 
+def dense_weight(w, x):
+    """A layer weight as the dense tensor the training / prefill kernels take: ``w`` itself,
+    or for an ``ops.Fp8Weight`` a transient dequantised image in ``x``'s dtype (exact: see
+    ops/skinny_fp8.py), which is inference only."""
+    if not isinstance(w, ops.Fp8Weight):
+        return w
+    if torch.is_grad_enabled() or _tape.current() is not None:
+        raise RuntimeError("a model with quantised weights is inference only: run it under torch.no_grad() "
+                           "and without the autograd tape")
+    return w.dequant(x.dtype)
+
+
+def _quantized_state_error(*args, **kwargs):
+    raise NotImplementedError("state_dict() / load_state_dict() of a model with quantised weights is not "
+                              "implemented: load the bf16 checkpoint first, then call quantize_weights()")
+
+
 class GenerationMixin:
     """KV-cache inference for a causal LM (see the module docstring for the hooks)."""
+
+    # per decoder layer, the names of the matrices quantize_weights() converts (set by the model)
+    _quant_weights = ()
+
+    @torch.no_grad()
+    def quantize_weights(self, fmt="fp8_e4m3", include_head=False):
+        """Weight-only quantisation for generation: every decoder layer's matrices (and with
+        ``include_head`` an untied ``lm_head``) become ``ops.Fp8Weight``s -- e4m3 codes plus
+        one power-of-two fp32 scale per output column -- and the bf16 parameters are dropped.
+        Embeddings, norms, biases and a tied head stay as they are.  ``decode_step`` then runs
+        the same ops with those products on the e4m3 weight-streaming kernel; prefill and
+        ``model(ids)`` run the usual kernels on a transient dequantised image of one layer
+        matrix (the two MLP matrices of a fused SwiGLU block) at a time, which is exact.
+        The model is inference only afterwards.  Returns ``self``."""
+        if fmt != "fp8_e4m3":
+            raise ValueError(f"quantize_weights: unknown fmt {fmt!r} (supported: 'fp8_e4m3')")
+        if getattr(self, "_pa_quantized", None) is not None:
+            raise RuntimeError(f"quantize_weights: the weights are already quantised ({self._pa_quantized})")
+        if getattr(self, "tp", None) is not None:
+            raise NotImplementedError("quantize_weights() with tensor parallelism is not implemented")
+        if not self._quant_weights:
+            raise NotImplementedError(f"quantize_weights() is not implemented for {type(self).__name__}")
+        if include_head and getattr(self, "lm_head", None) is None:
+            raise ValueError("quantize_weights: include_head=True needs an untied lm_head")
+        targets = [(layer, n) for layer in self.layers for n in self._quant_weights]
+        if include_head:
+            targets.append((self, "lm_head"))
+        for mod, n in targets:  # before anything is changed
+            if not torch.isfinite(getattr(mod, n)).all():
+                raise ValueError(f"quantize_weights: {n} has a non-finite value")
+        for mod, n in targets:
+            w8 = ops.quantize_weight_fp8(getattr(mod, n).detach())
+            delattr(mod, n)  # the parameter (and whatever ops cached on it) goes
+            setattr(mod, n, w8)
+        self._pa_quantized = fmt
+        self.state_dict = self.load_state_dict = self.set_state_dict = _quantized_state_error
+        return self.eval()
 
     def _check_generation_supported(self):
         if getattr(self, "tp", None) is not None:

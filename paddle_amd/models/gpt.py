@@ -23,7 +23,7 @@ import torch
 from .. import ops
 from ..autograd import tape as _tape
 from ..nn import Layer
-from .generation import GenerationMixin, prefill_qkv_attention
+from .generation import GenerationMixin, dense_weight, prefill_qkv_attention
 from .llama import _dt, _param
 
 
@@ -100,7 +100,7 @@ class GPTDecoderLayer(Layer):
         # bias of a row-parallel GEMM is added once, after the all-reduce; without
         # TP it rides the GEMM epilogue
         if not self.tp:
-            return ops.linear(x, w, b)
+            return ops.linear(x, dense_weight(w, x), b)
         return ops.add(self.tp.reduce_from_region(ops.linear(x, w)), b)
 
     def forward(self, x, residual=None):
@@ -113,12 +113,13 @@ class GPTDecoderLayer(Layer):
         if self.tp:
             y = self.tp.copy_to_region(y)
         # packed q|k|v straight into the attention kernel; dqkv comes back packed
-        a = ops.packed_attention(ops.linear(y, self.qkv_w, self.qkv_b), self.nh, causal=True)
+        a = ops.packed_attention(ops.linear(y, dense_weight(self.qkv_w, y), self.qkv_b), self.nh, causal=True)
         a = self._row_linear(a, self.out_w, self.out_b)
         y2, h2 = ops.layer_norm(a, self.ln2_w, self.ln2_b, eps, residual=h)
         if self.tp:
             y2 = self.tp.copy_to_region(y2)
-        m = self._row_linear(ops.linear_gelu(y2, self.fc1_w, self.fc1_b), self.fc2_w, self.fc2_b)
+        m = ops.linear_gelu(y2, dense_weight(self.fc1_w, y2), self.fc1_b)
+        m = self._row_linear(m, self.fc2_w, self.fc2_b)
         return m, h2
 
     def forward_cached(self, x, residual, cache, layer_idx, prefill):
@@ -132,7 +133,8 @@ class GPTDecoderLayer(Layer):
         else:
             y, h = ops.layer_norm(x, self.ln1_w, self.ln1_b, eps, residual=residual)
         if prefill:
-            packed, a = prefill_qkv_attention(y, self.qkv_w, self.qkv_b, None, None, self.nh, self.nh)
+            qkv_w = dense_weight(self.qkv_w, y)
+            packed, a = prefill_qkv_attention(y, qkv_w, self.qkv_b, None, None, self.nh, self.nh)
             ops.kv_append(packed, cache, layer_idx, self.nh, self.nh)
         else:
             # decode: M = B rows per product, weight-streaming kernels (ops/skinny.py)
@@ -142,9 +144,10 @@ class GPTDecoderLayer(Layer):
             y2, h2 = ops.layer_norm(a, self.ln2_w, self.ln2_b, eps, residual=h)
             m = ops.skinny_linear(y2, self.fc1_w, self.fc1_b, act="gelu_tanh")
             return ops.skinny_linear(m, self.fc2_w, self.fc2_b), h2
-        a = ops.linear(a, self.out_w, self.out_b)
+        a = ops.linear(a, dense_weight(self.out_w, a), self.out_b)
         y2, h2 = ops.layer_norm(a, self.ln2_w, self.ln2_b, eps, residual=h)
-        return ops.linear(ops.linear_gelu(y2, self.fc1_w, self.fc1_b), self.fc2_w, self.fc2_b), h2
+        m = ops.linear_gelu(y2, dense_weight(self.fc1_w, y2), self.fc1_b)
+        return ops.linear(m, dense_weight(self.fc2_w, m), self.fc2_b), h2
 
 
 class GPTEmbeddings(Layer):
@@ -172,6 +175,8 @@ class GPTEmbeddings(Layer):
 
 
 class GPTForCausalLM(Layer, GenerationMixin):
+    _quant_weights = ("qkv_w", "out_w", "fc1_w", "fc2_w")
+
     def __init__(self, cfg: GPTConfig, device=None, tp=None):
         super().__init__("gpt")
         self.cfg, self.tp = cfg, _tp_on(tp)

@@ -27,7 +27,7 @@ import torch
 from .. import ops
 from ..autograd import tape as _tape
 from ..nn import Layer
-from .generation import GenerationMixin, prefill_qkv_attention
+from .generation import GenerationMixin, dense_weight, prefill_qkv_attention
 
 
 @dataclass
@@ -153,25 +153,23 @@ class LlamaDecoderLayer(Layer):
         if self.tp is not None:
             y = self.tp.copy_to_region(y)
         # QKV projection with the rotary in its epilogue, then flash attention (one node)
-        a = ops.qkv_rope_attention(y, self.qkv_proj, cos, sin, self.nh, self.nkv, causal=True)
-        a = ops.linear(a, self.o_proj)
+        a = ops.qkv_rope_attention(y, dense_weight(self.qkv_proj, y), cos, sin, self.nh, self.nkv, causal=True)
+        a = ops.linear(a, dense_weight(self.o_proj, a))
         if self.tp is not None:
             a = self.tp.reduce_from_region(a)
         y2, h2 = ops.rms_norm(a, self.post_attention_layernorm, eps, residual=h)
         if self.tp is not None:
             y2 = self.tp.copy_to_region(y2)
-        if self.mlp_interleaved:
-            m = ops.swiglu_mlp(y2, self.gate_up_proj, self.down_proj)
-        else:
-            m = ops.linear(ops.swiglu(ops.linear(y2, self.gate_up_proj)), self.down_proj)
+        m = self._mlp(y2)
         if self.tp is not None:
             m = self.tp.reduce_from_region(m)
         return m, h2
 
     def _mlp(self, y2):
         if self.mlp_interleaved:
-            return ops.swiglu_mlp(y2, self.gate_up_proj, self.down_proj)
-        return ops.linear(ops.swiglu(ops.linear(y2, self.gate_up_proj)), self.down_proj)
+            return ops.swiglu_mlp(y2, dense_weight(self.gate_up_proj, y2), dense_weight(self.down_proj, y2))
+        hm = ops.swiglu(ops.linear(y2, dense_weight(self.gate_up_proj, y2)))
+        return ops.linear(hm, dense_weight(self.down_proj, hm))
 
     def forward_cached(self, x, residual, cos, sin, cache, layer_idx, prefill):
         """``forward`` for inference with a KV cache (no tensor parallelism).  Prefill: the
@@ -185,7 +183,8 @@ class LlamaDecoderLayer(Layer):
         else:
             y, h = ops.rms_norm(x, self.input_layernorm, eps, residual=residual)
         if prefill:
-            packed, a = prefill_qkv_attention(y, self.qkv_proj, None, cos, sin, self.nh, self.nkv)
+            qkv_w = dense_weight(self.qkv_proj, y)
+            packed, a = prefill_qkv_attention(y, qkv_w, None, cos, sin, self.nh, self.nkv)
             ops.kv_append(packed, cache, layer_idx, self.nh, self.nkv)
         else:
             # decode: M = B rows per product, weight-streaming kernels (ops/skinny.py)
@@ -198,7 +197,7 @@ class LlamaDecoderLayer(Layer):
             else:
                 hm = ops.swiglu(ops.skinny_linear(y2, self.gate_up_proj))
             return ops.skinny_linear(hm, self.down_proj), h2
-        a = ops.linear(a, self.o_proj)
+        a = ops.linear(a, dense_weight(self.o_proj, a))
         y2, h2 = ops.rms_norm(a, self.post_attention_layernorm, eps, residual=h)
         return self._mlp(y2), h2
 
@@ -207,6 +206,8 @@ class LlamaForCausalLM(Layer, GenerationMixin):
     """``tp``: optional ``distributed.fleet.TPGroup`` -- Megatron tensor parallelism:
     QKV / gate|up column-parallel, o / down row-parallel (one all-reduce each),
     vocab-parallel embedding, vocab-sharded LM head + parallel cross entropy."""
+
+    _quant_weights = ("qkv_proj", "o_proj", "gate_up_proj", "down_proj")
 
     def __init__(self, cfg: LlamaConfig, device=None, tp=None):
         super().__init__("llama")
@@ -263,7 +264,7 @@ class LlamaForCausalLM(Layer, GenerationMixin):
                 return logits
             return parallel_cross_entropy(logits, labels, self.tp.group)
         if self.lm_head is not None:
-            logits = ops.linear(y, self.lm_head)
+            logits = ops.linear(y, dense_weight(self.lm_head, y))
         else:
             logits = ops.linear_t(y, self.embed_tokens)
         if labels is None:

@@ -8,3 +8,5 @@ from .fused import (apply_rotary, embedding, flash_attention, flash_attention_va
 from .decode import KVCache, PagedKVCache, kv_append, decode_attention  # noqa: F401
 from . import skinny  # noqa: F401
 from .skinny import skinny_ok, skinny_linear, skinny_linear_t, skinny_default_splits  # noqa: F401
+from . import skinny_fp8  # noqa: F401
+from .skinny_fp8 import Fp8Weight, quantize_weight_fp8, skinny_fp8_ok, skinny_fp8_default_splits  # noqa: F401

@@ -78,6 +78,12 @@ _SIGS = {
     "pa_gemm_skinny_splits": [_I, _I, _I],
     "pa_gemm_skinny_ws_floats": [_I, _I, _I],
     "pa_gemm_skinny": [_I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _L, _L, _L, _I, _I, _P],
+    "pa_gemm_skinny_f8_set_tile": [_I],
+    "pa_gemm_skinny_f8_ok": [_I, _I, _I, _L, _L, _L, _I, _I, _P, _P, _P, _P, _P],
+    "pa_gemm_skinny_f8_splits": [_I, _I],
+    "pa_gemm_skinny_f8_ws_floats": [_I, _I, _I],
+    "pa_gemm_skinny_f8": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _L, _L, _L, _I, _I, _P],
+    "pa_fp8w_dequant": [_P, _P, _P, _L, _L, _L, _L, _P],
     "pa_fa_bwd_set_variant": [_I],
     "pa_fa_fwd_set_variant": [_I],
     "pa_fa_bwd_get_variant": [],

@@ -23,6 +23,7 @@ import torch
 from ..utils import flags as _flags
 from . import _native as N
 from . import fused as F
+from . import skinny_fp8 as _F8
 
 __all__ = ["skinny_ok", "skinny_linear", "skinny_linear_t", "skinny_default_splits"]
 
@@ -142,7 +143,8 @@ def skinny_kernel(x, w, *, b_kmaj=False, bias=None, act=None, num_splits=None):
 
 @torch.no_grad()
 def skinny_linear(x, w, bias=None, act=None, num_splits=None):
-    """x [..., K] (at most 16 rows) times w [K, N] with an optional epilogue:
+    """x [..., K] (at most 16 rows) times w [K, N] (a bf16 tensor or an ``ops.Fp8Weight``) with
+    an optional epilogue:
 
     * ``act=None``: ``x w (+ bias)`` -- ``ops.linear``;
     * ``act="gelu_tanh"``: ``gelu(x w + bias)`` -- ``ops.linear_gelu``;
@@ -150,6 +152,13 @@ def skinny_linear(x, w, bias=None, act=None, num_splits=None):
       ``ops.interleave_gate_up``; returns ``silu(gate) * up`` [..., N/2]."""
     if act not in _ACTS:
         raise ValueError(f"skinny_linear: unknown act {act!r}")
+    if isinstance(w, _F8.Fp8Weight):
+        # e4m3 weight (ops/skinny_fp8.py): its own kernel where routed, else the expressions
+        # below on the dequantised weight, which is exact
+        out = _F8.linear(x, w, bias, act, num_splits)
+        if out is not None:
+            return out
+        w, num_splits = _F8.dequant_for(x, w), None
     prob = _problem(x, w, False, bias, act, num_splits)
     if prob is not None:
         return _run(prob, x, w, False, bias)
