@@ -18,6 +18,10 @@ Cache layout: see :mod:`paddle_amd.ops.decode` (one slab per layer, the default)
 row's first decoded token overwrites the first padding slot of a short prompt: positions
 are per row (``cache.lens``).
 
+``generate(graph=True)`` samples with the device kernel of :mod:`paddle_amd.ops.sampling`
+and replays one captured decode step (:class:`DecodeGraph`: step, sampler and ``advance``
+in one HIP graph) instead of launching it from Python every token.
+
 ``quantize_weights()`` turns the decoder layers' matrices into ``ops.Fp8Weight``s (e4m3 codes,
 power-of-two column scales): decode steps run them on the fp8 weight-streaming kernel,
 prefill on an exact dequantised image (ops/skinny_fp8.py).
@@ -25,6 +29,7 @@ prefill on an exact dequantised image (ops/skinny_fp8.py).
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 
@@ -75,12 +80,10 @@ def prefill_qkv_attention(y, w, bias, cos, sin, Hq, Hk):
     return packed, o.reshape(B, S, Hq * D)
 
 
-def sample_next(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, generator=None):
-    """Next token per row from logits [B, V] (fp32 math): greedy, or temperature /
-    top-k / top-p (nucleus) sampling with ``generator`` driving the draws."""
+def filter_logits(logits, temperature=1.0, top_k=0, top_p=1.0):
+    """The fp32 logits ``sample_next`` draws from: scaled by the temperature, with ``-inf``
+    where top-k / top-p (nucleus) filtering drops a token."""
     logits = logits.float()
-    if not do_sample:
-        return logits.argmax(-1)
     if temperature != 1.0:
         logits = logits / max(float(temperature), 1e-6)
     V = logits.shape[-1]
@@ -94,7 +97,15 @@ def sample_next(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, ge
         drop = (sp.cumsum(-1) - sp) >= float(top_p)
         sl = sl.masked_fill(drop, float("-inf"))
         logits = torch.full_like(logits, float("-inf")).scatter(-1, si, sl)
-    probs = torch.softmax(logits, -1)
+    return logits
+
+
+def sample_next(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, generator=None):
+    """Next token per row from logits [B, V] (fp32 math): greedy, or temperature /
+    top-k / top-p (nucleus) sampling with ``generator`` driving the draws."""
+    if not do_sample:
+        return logits.float().argmax(-1)
+    probs = torch.softmax(filter_logits(logits, temperature, top_k, top_p), -1)
     return torch.multinomial(probs, 1, generator=generator).squeeze(-1)
 
 
@@ -113,6 +124,99 @@ def dense_weight(w, x):
 def _quantized_state_error(*args, **kwargs):
     raise NotImplementedError("state_dict() / load_state_dict() of a model with quantised weights is not "
                               "implemented: load the bf16 checkpoint first, then call quantize_weights()")
+
+
+class DecodeGraph:
+    """One decode step -- ``embed(state.tok)`` -> layers -> logits -> ``ops.sample_step`` ->
+    ``cache.advance`` -- captured once into a HIP graph and replayed by :meth:`step`.
+
+    ``state`` is an ``ops.SamplerState`` whose ``tok`` holds the token to feed (seed it with one
+    eager ``ops.sample_step`` on the prefill logits).  ``logits`` is the static [B, V] buffer
+    of the last replay.  The object keeps the cache, the state and the graph's private memory
+    pool alive.  The capture runs on one stream, so the graph is a linear chain of the
+    launches of ``decode_step`` + ``sample_step``, with their split counts: a replay computes
+    the bits of the launch loop.
+
+    Capture records the launches without running them, but the Python side of the step runs,
+    so the host mirrors of the cache lengths are put back after the capture and advanced by
+    one per replay.  A paged cache reserves the blocks of ``steps`` more tokens per row before
+    the capture (``ValueError`` with nothing changed when the pool is short): the block table
+    is constant from then on, and no upload happens inside the capture or between replays.
+
+    On the CPU (or any cache that is not on a GPU) there is no graph: :meth:`step` runs the
+    same sequence eagerly on the same state."""
+
+    def __init__(self, model, cache, state, steps=None, seed=0, do_sample=False, temperature=1.0, top_k=0,
+                 top_p=1.0):
+        model._check_generation_supported()
+        if state.batch != cache.batch:
+            raise ValueError(f"decode_graph: a state of {state.batch} rows for a cache of {cache.batch}")
+        self.model, self.cache, self.state = model, cache, state
+        self._sampling = (int(seed), bool(do_sample), float(temperature), int(top_k or 0), float(top_p))
+        self._paged = getattr(cache, "paged", False)
+        room = cache.max_len - cache.bound
+        self.steps = min(state.max_new_tokens, room) if steps is None else int(steps)
+        if self.steps < 1:
+            raise ValueError(f"KV cache overflow: {cache.bound} cached + 1 new tokens > max_len {cache.max_len}")
+        if self._paged:
+            cache.reserve(self.steps)  # raises, with nothing changed, when the pool (or max_len) is short
+        self._left = self.steps
+        self._epoch = cache._epoch
+        self.replays = 0
+        self.graph = None
+        self.logits = None
+        if cache.lens.is_cuda:
+            self._capture()
+
+    def _body(self):
+        logits = self.model.decode_step(self.state.tok, self.cache)
+        ops.sample_step(logits, self.state, *self._sampling)
+        return logits
+
+    def _capture(self):
+        model, cache, st = self.model, self.cache, self.state
+        mirror = cache._mirror()
+        # warm-up, eagerly and off the capture: everything the step creates on first use (code
+        # objects, cached buffers) exists before the capture.  It leaves no trace: the keys and
+        # values it writes land in the slots the first replay rewrites, lens and state stay.
+        side = torch.cuda.Stream(device=cache.lens.device)
+        side.wait_stream(torch.cuda.current_stream(cache.lens.device))
+        with torch.cuda.stream(side):
+            logits = model._lm_logits(model._decode_hidden(st.tok.reshape(-1, 1), cache).reshape(st.batch, -1))
+            N.call("pa_i32_add", N.ptr(cache.lens), cache.batch, 0, N.stream())
+            ops.sample_tokens(logits, *self._sampling[:1], st.step, *self._sampling[1:])
+            del logits
+        torch.cuda.current_stream(cache.lens.device).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        try:
+            with torch.cuda.graph(self.graph):
+                self.logits = self._body()
+        finally:
+            cache._set_mirror(mirror)  # recorded, not run: the device lengths have not moved
+
+    def _check_usable(self):
+        cache = self.cache
+        if cache._epoch != self._epoch:
+            raise RuntimeError("DecodeGraph: the cache was reset or rows were freed after the capture; "
+                               "capture a new graph")
+        if cache.bound + 1 > cache.max_len:
+            raise ValueError(f"KV cache overflow: {cache.bound} cached + 1 new tokens > max_len {cache.max_len}")
+        if self._paged and self._left < 1:
+            raise ValueError(f"DecodeGraph: the blocks of {self.steps} steps were reserved at capture and are used up")
+
+    def step(self):
+        """One decode step: replay the graph (no launch from Python) and advance the host
+        mirrors by one.  Raises before anything runs when the cache is full, when the steps
+        reserved at capture are used up (paged) or when the cache was reset since."""
+        self._check_usable()
+        if self.graph is None:
+            self.logits = self._body()
+        else:
+            self.graph.replay()
+            self.cache._advance_mirror(1)
+        self._left -= 1
+        self.replays += 1
+        return self.state.tok
 
 
 class GenerationMixin:
@@ -247,8 +351,16 @@ class GenerationMixin:
         return self._lm_logits(y.reshape(y.shape[0], -1))
 
     @torch.no_grad()
+    def decode_graph(self, cache, state, steps=None, seed=0, do_sample=False, temperature=1.0, top_k=0, top_p=1.0):
+        """Capture one decode step on ``cache`` and ``state`` (an ``ops.SamplerState``) for
+        ``steps`` replays (default: what ``state`` and the cache have room for); see
+        :class:`DecodeGraph`."""
+        return DecodeGraph(self, cache, state, steps, seed, do_sample, temperature, top_k, top_p)
+
+    @torch.no_grad()
     def generate(self, input_ids, max_new_tokens, prompt_lens=None, do_sample=False, temperature=1.0, top_k=0,
-                 top_p=1.0, eos_token_id=None, pad_token_id=0, seed=None, cache="contiguous", block_size=None):
+                 top_p=1.0, eos_token_id=None, pad_token_id=0, seed=None, cache="contiguous", block_size=None,
+                 graph=False, sampler=None):
         """Generate ``max_new_tokens`` tokens after the right-padded prompts ``input_ids``
         [B, S] (``prompt_lens``: valid length per row, default S).
 
@@ -259,8 +371,22 @@ class GenerationMixin:
         ``cache="paged"`` keeps the keys and values in blocks of ``block_size`` tokens from
         a pool of ``sum_b ceil((prompt_len_b + max_new_tokens) / block_size)`` blocks --
         what the rows can reach, not ``B * (S + max_new_tokens)`` slots; the tokens are the
-        same."""
+        same.
+
+        ``sampler``: ``"torch"`` (``sample_next`` with a ``torch.Generator``; the default) or
+        ``"philox"`` (``ops.sample_step``: the device kernel, the counter-based generator and
+        the bookkeeping on the device, no ATen launches between steps; with ``seed=None`` a
+        random seed).  ``graph=True`` captures one decode step after the prefill and replays
+        it for the remaining tokens (:class:`DecodeGraph`); it needs, and defaults to, the
+        ``"philox"`` sampler.  Greedy tokens are the same on every path; sampled tokens differ
+        between the two samplers, which draw different random numbers."""
         self._check_generation_supported()
+        if sampler is None:
+            sampler = "philox" if graph else "torch"
+        if sampler not in ("torch", "philox"):
+            raise ValueError(f"generate: sampler must be 'torch' or 'philox', got {sampler!r}")
+        if graph and sampler != "philox":
+            raise ValueError("generate: graph=True needs sampler='philox' (a torch.Generator draw does not replay)")
         if cache not in ("contiguous", "paged"):
             raise ValueError(f"generate: cache must be 'contiguous' or 'paged', got {cache!r}")
         if block_size is not None and cache != "paged":
@@ -274,7 +400,7 @@ class GenerationMixin:
                              f"({self.cfg.max_position_embeddings})")
         dev = input_ids.device
         gen = None
-        if do_sample:
+        if do_sample and sampler == "torch":
             gen = torch.Generator(device=dev)
             if seed is not None:
                 gen.manual_seed(int(seed))
@@ -288,6 +414,19 @@ class GenerationMixin:
                                     num_blocks=sum(-(-(n + max_new_tokens) // bs) for n in plens))
         else:
             cache = self.init_cache(B, S + max_new_tokens)
+        if sampler == "philox":
+            seed = int.from_bytes(os.urandom(8), "little") if seed is None else int(seed)
+            how = (seed, do_sample, temperature, top_k, top_p)
+            st = ops.SamplerState(B, max_new_tokens, dev, eos_token_id, pad_token_id)
+            ops.sample_step(self.prefill(input_ids, cache, prompt_lens), st, *how)
+            if max_new_tokens > 1 and graph:
+                g = self.decode_graph(cache, st, max_new_tokens, *how)
+                for _ in range(max_new_tokens - 1):
+                    g.step()
+            else:
+                for _ in range(max_new_tokens - 1):
+                    ops.sample_step(self.decode_step(st.tok, cache), st, *how)
+            return st.out, st.lengths
         out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=torch.long, device=dev)
         lengths = torch.full((B,), max_new_tokens, dtype=torch.long, device=dev)
         done = torch.zeros(B, dtype=torch.bool, device=dev)

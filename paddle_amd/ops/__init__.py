@@ -10,3 +10,5 @@ from . import skinny  # noqa: F401
 from .skinny import skinny_ok, skinny_linear, skinny_linear_t, skinny_default_splits  # noqa: F401
 from . import skinny_fp8  # noqa: F401
 from .skinny_fp8 import Fp8Weight, quantize_weight_fp8, skinny_fp8_ok, skinny_fp8_default_splits  # noqa: F401
+from . import sampling  # noqa: F401
+from .sampling import SamplerState, philox_uniform, sample_step, sample_tokens  # noqa: F401

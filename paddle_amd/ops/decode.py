@@ -43,6 +43,7 @@ class KVCache:
         self.v = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in range(self.num_layers)]
         self.lens = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
         self._bound = 0  # host-side upper bound of lens
+        self._epoch = 0  # bumped by reset(): a captured decode graph of an earlier epoch is stale
 
     @property
     def bound(self) -> int:
@@ -52,6 +53,18 @@ class KVCache:
         """Forget every cached token (the storage is kept)."""
         self.lens.zero_()
         self._bound = 0
+        self._epoch += 1
+
+    # the host mirror of lens, for a decode step that is captured (recorded, not run) and
+    # replayed (run without its Python side): models/generation.py DecodeGraph
+    def _mirror(self):
+        return self._bound
+
+    def _set_mirror(self, m):
+        self._bound = int(m)
+
+    def _advance_mirror(self, T: int = 1):
+        self._bound += int(T)
 
     def check_room(self, T: int):
         if self._bound + int(T) > self.max_len:

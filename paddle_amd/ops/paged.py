@@ -77,6 +77,7 @@ class PagedKVCache:
         self._in_prefill = False
         self._slack = None  # cached: tokens every row can still take in the blocks it owns
         self._bound = None  # cached: max of _lens
+        self._epoch = 0  # bumped when rows lose their blocks: a captured decode graph is stale then
 
     # ------------------------------------------------------------------ host views
     @property
@@ -88,6 +89,19 @@ class PagedKVCache:
     def _changed(self):
         """The lengths or the ownership changed: drop what was derived from them."""
         self._slack = self._bound = None
+
+    # the host mirror of lens, for a decode step that is captured (recorded, not run) and
+    # replayed (run without its Python side): models/generation.py DecodeGraph
+    def _mirror(self):
+        return list(self._lens)
+
+    def _set_mirror(self, m):
+        self._lens = [int(n) for n in m]
+        self._changed()
+
+    def _advance_mirror(self, T: int = 1):
+        self._lens = [n + int(T) for n in self._lens]
+        self._changed()
 
     @property
     def host_lens(self):
@@ -199,6 +213,7 @@ class PagedKVCache:
             self._table[r].fill_(-1)
             self._lens[r] = 0
         self._changed()
+        self._epoch += 1
         self._upload_table()
         self._upload_lens()
 
@@ -210,6 +225,7 @@ class PagedKVCache:
         self._table.fill_(-1)
         self._lens = [0] * self.batch
         self._changed()
+        self._epoch += 1
         self.block_table.fill_(-1)
         self.lens.zero_()
 
@@ -259,6 +275,7 @@ class PagedKVCache:
         self._free = [b for b in range(self.num_blocks - 1, -1, -1) if b not in seen]
         self._lens = [0] * self.batch
         self._changed()
+        self._epoch += 1
         self._upload_table()
         self._upload_lens()
 
