@@ -22,6 +22,9 @@ are per row (``cache.lens``).
 and replays one captured decode step (:class:`DecodeGraph`: step, sampler and ``advance``
 in one HIP graph) instead of launching it from Python every token.
 
+``kv_dtype="fp8_e4m3"`` (``init_cache`` / ``generate``) keeps either cache in e4m3 codes with
+one power-of-two scale per (token, kv head): ops/kv_fp8.py.
+
 ``quantize_weights()`` turns the decoder layers' matrices into ``ops.Fp8Weight``s (e4m3 codes,
 power-of-two column scales): decode steps run them on the fp8 weight-streaming kernel,
 prefill on an exact dequantised image (ops/skinny_fp8.py).
@@ -266,10 +269,13 @@ class GenerationMixin:
     def _gen_device(self):
         return next(self.parameters()).device
 
-    def init_cache(self, batch: int, max_len: int, paged: bool = False, block_size=None, num_blocks=None):
+    def init_cache(self, batch: int, max_len: int, paged: bool = False, block_size=None, num_blocks=None,
+                   kv_dtype=None):
         """An empty cache for ``batch`` rows of up to ``max_len`` tokens each: one slab per
         layer, or with ``paged=True`` a pool of ``num_blocks`` blocks of ``block_size``
-        tokens (default: ``batch * ceil(max_len / block_size)``, the slab's capacity)."""
+        tokens (default: ``batch * ceil(max_len / block_size)``, the slab's capacity).
+        ``kv_dtype="fp8_e4m3"``: either layout stores e4m3 codes and one power-of-two scale
+        per (token, kv head) (ops/kv_fp8.py); ``None``: the model's dtype."""
         self._check_generation_supported()
         cfg = self.cfg
         if max_len > cfg.max_position_embeddings:
@@ -279,10 +285,10 @@ class GenerationMixin:
         p = next(self.parameters())
         if paged:
             return PagedKVCache(cfg.num_hidden_layers, batch, max_len, kvh, cfg.head_dim, p.dtype, p.device,
-                                block_size=block_size, num_blocks=num_blocks)
+                                block_size=block_size, num_blocks=num_blocks, kv_dtype=kv_dtype)
         if block_size is not None or num_blocks is not None:
             raise ValueError("init_cache: block_size / num_blocks need paged=True")
-        return KVCache(cfg.num_hidden_layers, batch, max_len, kvh, cfg.head_dim, p.dtype, p.device)
+        return KVCache(cfg.num_hidden_layers, batch, max_len, kvh, cfg.head_dim, p.dtype, p.device, kv_dtype=kv_dtype)
 
     @torch.no_grad()
     def prefill(self, input_ids, cache, prompt_lens=None, rows=None):
@@ -360,7 +366,7 @@ class GenerationMixin:
     @torch.no_grad()
     def generate(self, input_ids, max_new_tokens, prompt_lens=None, do_sample=False, temperature=1.0, top_k=0,
                  top_p=1.0, eos_token_id=None, pad_token_id=0, seed=None, cache="contiguous", block_size=None,
-                 graph=False, sampler=None):
+                 graph=False, sampler=None, kv_dtype=None):
         """Generate ``max_new_tokens`` tokens after the right-padded prompts ``input_ids``
         [B, S] (``prompt_lens``: valid length per row, default S).
 
@@ -372,6 +378,10 @@ class GenerationMixin:
         a pool of ``sum_b ceil((prompt_len_b + max_new_tokens) / block_size)`` blocks --
         what the rows can reach, not ``B * (S + max_new_tokens)`` slots; the tokens are the
         same.
+
+        ``kv_dtype="fp8_e4m3"`` keeps either cache in e4m3 with one scale per (token, kv
+        head): half the bytes, and the tokens of a run whose cache holds the dequantised
+        values (ops/kv_fp8.py).  Prefill attends to the unquantised prompt.
 
         ``sampler``: ``"torch"`` (``sample_next`` with a ``torch.Generator``; the default) or
         ``"philox"`` (``ops.sample_step``: the device kernel, the counter-based generator and
@@ -391,6 +401,7 @@ class GenerationMixin:
             raise ValueError(f"generate: cache must be 'contiguous' or 'paged', got {cache!r}")
         if block_size is not None and cache != "paged":
             raise ValueError("generate: block_size needs cache='paged'")
+        ops.kv_fp8.check_kv_dtype(kv_dtype)
         B, S = input_ids.shape
         max_new_tokens = int(max_new_tokens)
         if max_new_tokens < 1:
@@ -411,9 +422,9 @@ class GenerationMixin:
             plens = [S] * B if prompt_lens is None else [int(x) for x in (
                 prompt_lens.tolist() if torch.is_tensor(prompt_lens) else prompt_lens)]
             cache = self.init_cache(B, S + max_new_tokens, paged=True, block_size=bs,
-                                    num_blocks=sum(-(-(n + max_new_tokens) // bs) for n in plens))
+                                    num_blocks=sum(-(-(n + max_new_tokens) // bs) for n in plens), kv_dtype=kv_dtype)
         else:
-            cache = self.init_cache(B, S + max_new_tokens)
+            cache = self.init_cache(B, S + max_new_tokens, kv_dtype=kv_dtype)
         if sampler == "philox":
             seed = int.from_bytes(os.urandom(8), "little") if seed is None else int(seed)
             how = (seed, do_sample, temperature, top_k, top_p)

@@ -74,6 +74,15 @@ _SIGS = {
     "pa_kv_append_paged": [_P, _LP, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P],
     "pa_attn_decode_paged_ok": [_I, _I, _I, _I, _I, _I, _LP, _I, _I, _I],
     "pa_attn_decode_paged": [_P, _LP, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
+    "pa_kv_append_f8_ok": [_I],
+    "pa_kv_append_f8": [_P, _LP, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
+    "pa_kv_append_paged_f8_ok": [_I, _I],
+    "pa_kv_append_paged_f8": [_P, _LP, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I,
+                              _I, _P],
+    "pa_attn_decode_f8_ok": [_I, _I, _I, _I, _I, _I, _LP],
+    "pa_attn_decode_f8": [_P, _LP, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
+    "pa_attn_decode_paged_f8_ok": [_I, _I, _I, _I, _I, _I, _LP, _I, _I, _I],
+    "pa_attn_decode_paged_f8": [_P, _LP, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
     "pa_gemm_skinny_ok": [_I, _I, _I, _I, _L, _L, _L, _I, _I, _P, _P, _P, _P],
     "pa_gemm_skinny_splits": [_I, _I, _I],
     "pa_gemm_skinny_ws_floats": [_I, _I, _I],

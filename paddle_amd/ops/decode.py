@@ -13,6 +13,12 @@ reads ``lens`` back to the host.
 
 ``PagedKVCache`` (:mod:`paddle_amd.ops.paged`) stores the same tokens in fixed-size blocks
 from a shared pool; ``kv_append`` and ``decode_attention`` take either cache.
+
+``kv_dtype="fp8_e4m3"`` (either cache) stores e4m3 codes in the same layout plus one
+power-of-two fp32 scale per (token, kv head) in ``k_scale`` / ``v_scale`` ``[B, max_len, Hk]``:
+the contract of :mod:`paddle_amd.ops.kv_fp8`.  ``kv_append`` quantises what the bf16 cache
+would have stored; ``decode_attention`` computes what it computes over a bf16 cache that
+holds ``cache.dequant(layer)``, bit for bit on the GPU kernels.
 """
 from __future__ import annotations
 
@@ -22,6 +28,7 @@ import torch
 
 from . import _native as N
 from .fused import _attn_ref, _check_scale, _fa_strides, ctypes_long_array
+from .kv_fp8 import _FP8, check_kv_dtype, dequantize_kv_fp8, quantize_kv_fp8
 
 __all__ = ["KVCache", "PagedKVCache", "kv_append", "decode_attention"]
 
@@ -34,13 +41,21 @@ class KVCache:
     device read.  One step is: ``kv_append`` + ``decode_attention`` per layer (both see
     the same ``lens``), then one ``advance(T)``."""
 
-    def __init__(self, num_layers, batch, max_len, num_kv_heads, head_dim, dtype=torch.bfloat16, device=None):
+    def __init__(self, num_layers, batch, max_len, num_kv_heads, head_dim, dtype=torch.bfloat16, device=None,
+                 kv_dtype=None):
+        self.kv_dtype = check_kv_dtype(kv_dtype)
         self.num_layers, self.batch, self.max_len = int(num_layers), int(batch), int(max_len)
         self.num_kv_heads, self.head_dim = int(num_kv_heads), int(head_dim)
         self.dtype, self.device = dtype, torch.device(device if device is not None else "cpu")
         shape = (self.batch, self.max_len, self.num_kv_heads, self.head_dim)
-        self.k = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in range(self.num_layers)]
-        self.v = [torch.zeros(shape, dtype=dtype, device=self.device) for _ in range(self.num_layers)]
+        store = _FP8 if self.quantized else dtype  # dtype stays what q, the output and dequant() have
+        self.k = [torch.zeros(shape, dtype=store, device=self.device) for _ in range(self.num_layers)]
+        self.v = [torch.zeros(shape, dtype=store, device=self.device) for _ in range(self.num_layers)]
+        if self.quantized:  # zero scales: a slot never written dequantises to 0
+            self.k_scale = [torch.zeros(shape[:3], dtype=torch.float32, device=self.device)
+                            for _ in range(self.num_layers)]
+            self.v_scale = [torch.zeros(shape[:3], dtype=torch.float32, device=self.device)
+                            for _ in range(self.num_layers)]
         self.lens = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
         self._bound = 0  # host-side upper bound of lens
         self._epoch = 0  # bumped by reset(): a captured decode graph of an earlier epoch is stale
@@ -48,6 +63,24 @@ class KVCache:
     @property
     def bound(self) -> int:
         return self._bound
+
+    @property
+    def quantized(self) -> bool:
+        return self.kv_dtype is not None
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of key / value storage: the elements (codes) plus, when quantised, the scales."""
+        ts = self.k + self.v + (self.k_scale + self.v_scale if self.quantized else [])
+        return sum(t.numel() * t.element_size() for t in ts)
+
+    def dequant(self, layer: int):
+        """(k, v) of ``layer`` as ``[B, max_len, Hk, D]`` in ``dtype``: ``codes * scale`` (exact) of
+        a quantised cache, the stored tensors otherwise."""
+        if not self.quantized:
+            return self.k[layer], self.v[layer]
+        return (dequantize_kv_fp8(self.k[layer], self.k_scale[layer], self.dtype),
+                dequantize_kv_fp8(self.v[layer], self.v_scale[layer], self.dtype))
 
     def reset(self):
         """Forget every cached token (the storage is kept)."""
@@ -107,9 +140,21 @@ def _kv_append_ref(q4, cache, layer, Hq, Hk, cos, sin):
     if cos is not None:
         q, k = _rope_at(q, cos, sin, positions), _rope_at(k, cos, sin, positions)
     bidx = torch.arange(B, device=q4.device).unsqueeze(1).expand(B, T)
-    cache.k[layer][bidx, positions] = k.to(cache.dtype)
-    cache.v[layer][bidx, positions] = v.to(cache.dtype)
+    _store_slots(cache, layer, (bidx, positions), k.to(cache.dtype), v.to(cache.dtype))
     return q.contiguous()
+
+
+def _store_slots(cache, layer, index, k, v):
+    """k / v [..., Hk, D] (what a cache in ``cache.dtype`` stores) into the slots ``index`` of
+    the [slots..., Hk, D] storage of ``layer``: as they are, or quantised by the contract."""
+    if not cache.quantized:
+        cache.k[layer][index] = k
+        cache.v[layer][index] = v
+        return
+    for x, codes, scales in ((k, cache.k[layer], cache.k_scale[layer]), (v, cache.v[layer], cache.v_scale[layer])):
+        c, s = quantize_kv_fp8(x)
+        codes.view(torch.uint8)[index] = c.view(torch.uint8)  # bytes: indexing is not defined on fp8
+        scales[index] = s
 
 
 def _aligned16(t):
@@ -119,6 +164,8 @@ def _aligned16(t):
 def _append_kernel_ok(q4, cache, cos, sin):
     D = q4.shape[-1]
     if not (q4.is_cuda and q4.dtype == torch.bfloat16 and cache.dtype == torch.bfloat16 and D % 16 == 0):
+        return False
+    if cache.quantized and not N.lib().pa_kv_append_f8_ok(int(D)):
         return False
     if q4.stride(-1) != 1 or any(s % 8 for s in q4.stride()[:3]) or not _aligned16(q4):
         return False
@@ -166,6 +213,12 @@ def kv_append(qkv, cache, layer: int, num_heads: int, num_kv_heads: int | None =
     if not _append_kernel_ok(q4, cache, cos, sin):
         return _kv_append_ref(q4, cache, layer, Hq, Hk, cos, sin)
     q = torch.empty(B, T, Hq, D, dtype=qkv.dtype, device=qkv.device)
+    if cache.quantized:
+        N.call("pa_kv_append_f8", N.ptr(q4), ctypes_long_array(_fa_strides(q4)), N.ptr(cache.lens), N.ptr(cos),
+               N.ptr(sin), int(cos.shape[0]) if cos is not None else 0, N.ptr(cache.k[layer]), N.ptr(cache.v[layer]),
+               N.ptr(cache.k_scale[layer]), N.ptr(cache.v_scale[layer]), cache.max_len, N.ptr(q), B, T, Hq, Hk, D,
+               N.stream())
+        return q
     N.call("pa_kv_append", N.ptr(q4), ctypes_long_array(_fa_strides(q4)), N.ptr(cache.lens), N.ptr(cos), N.ptr(sin),
            int(cos.shape[0]) if cos is not None else 0, N.ptr(cache.k[layer]), N.ptr(cache.v[layer]), cache.max_len,
            N.ptr(q), B, T, Hq, Hk, D, N.stream())
@@ -200,7 +253,9 @@ def decode_attention(q, cache, layer: int, scale: float | None = None, num_split
 
     On the GPU (bf16, D in {64, 128}, Hq/Hk in {1, 2, 4, 8}) the key axis is cut into
     ``num_splits`` ranges that run as separate workgroups and are merged by a second
-    kernel; the result is bit-identical from run to run for a given ``num_splits``."""
+    kernel; the result is bit-identical from run to run for a given ``num_splits``.  A
+    quantised cache runs the e4m3 instantiation of the same kernel (the bits of the bf16 one
+    over ``cache.dequant(layer)``); elsewhere it is the reference over ``cache.dequant(layer)``."""
     B, Tq, Hq, D = q.shape
     if Tq != 1 or B != cache.batch or D != cache.head_dim:
         raise ValueError(f"decode_attention: q {tuple(q.shape)} does not match the cache")
@@ -217,12 +272,21 @@ def decode_attention(q, cache, layer: int, scale: float | None = None, num_split
             and _aligned16(q) and kv_len.is_cuda and kv_len.dtype == torch.int32 and kv_len.is_contiguous():
         ns = default_num_splits(B, Hk, S_max) if num_splits is None else int(num_splits)
         qst = ctypes_long_array([q.stride(0), q.stride(2)])
-        if N.lib().pa_attn_decode_ok(B, S_max, Hq, Hk, D, ns, qst):
+        if cache.quantized:
+            if N.lib().pa_attn_decode_f8_ok(B, S_max, Hq, Hk, D, ns, qst):
+                o = torch.empty(B, 1, Hq, D, dtype=q.dtype, device=q.device)
+                ws = torch.empty(B * Hq * ns * (D + 2), dtype=torch.float32, device=q.device)
+                N.call("pa_attn_decode_f8", N.ptr(q), qst, N.ptr(k), N.ptr(v), N.ptr(cache.k_scale[layer]),
+                       N.ptr(cache.v_scale[layer]), N.ptr(kv_len), N.ptr(o), N.ptr(ws), B, S_max, Hq, Hk, D,
+                       float(scale), ns, N.stream())
+                return o
+        elif N.lib().pa_attn_decode_ok(B, S_max, Hq, Hk, D, ns, qst):
             o = torch.empty(B, 1, Hq, D, dtype=q.dtype, device=q.device)
             ws = torch.empty(B * Hq * ns * (D + 2), dtype=torch.float32, device=q.device)
             N.call("pa_attn_decode", N.ptr(q), qst, N.ptr(k), N.ptr(v), N.ptr(kv_len), N.ptr(o), N.ptr(ws),
                    B, S_max, Hq, Hk, D, float(scale), ns, N.stream())
             return o
+    k, v = cache.dequant(layer)
     return _decode_attention_ref(q, k, v, kv_len, float(scale))
 
 

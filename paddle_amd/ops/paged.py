@@ -11,6 +11,11 @@ LIFO free list.  No method reads the device; the table is uploaded only in the s
 that changed it.  ``ops.kv_append`` and ``ops.decode_attention`` dispatch here for a
 ``PagedKVCache`` (``pa_kv_append_paged`` / ``pa_attn_decode_paged`` of
 ``csrc/kernels/attn_decode.hip`` on the GPU in bf16, plain torch otherwise).
+
+``kv_dtype="fp8_e4m3"``: the pool holds e4m3 codes and a second pool ``k_scale[l]`` /
+``v_scale[l]`` ``[num_blocks, block_size, Hk]`` the fp32 scales, addressed through the same
+table (:mod:`paddle_amd.ops.kv_fp8`; ``pa_kv_append_paged_f8`` / ``pa_attn_decode_paged_f8``).
+The bookkeeping below does not know about the storage type.
 """
 from __future__ import annotations
 
@@ -21,6 +26,7 @@ import torch
 from . import _native as N
 from . import decode as _D
 from .fused import _fa_strides, ctypes_long_array
+from .kv_fp8 import _FP8, check_kv_dtype, dequantize_kv_fp8
 
 __all__ = ["PagedKVCache", "BLOCK_SIZES", "DEFAULT_BLOCK_SIZE"]
 
@@ -47,7 +53,8 @@ class PagedKVCache:
     paged = True
 
     def __init__(self, num_layers, batch, max_len, num_kv_heads, head_dim, dtype=torch.bfloat16, device=None,
-                 block_size=None, num_blocks=None, zero_fill=True):
+                 block_size=None, num_blocks=None, zero_fill=True, kv_dtype=None):
+        self.kv_dtype = check_kv_dtype(kv_dtype)
         block_size = DEFAULT_BLOCK_SIZE if block_size is None else int(block_size)
         if block_size not in BLOCK_SIZES:
             raise ValueError(f"block_size must be one of {BLOCK_SIZES}, got {block_size}")
@@ -63,9 +70,14 @@ class PagedKVCache:
         # one backing allocation, per-layer views
         alloc = torch.zeros if zero_fill else torch.empty
         self._pool = alloc((2, self.num_layers, self.num_blocks, block_size, self.num_kv_heads, self.head_dim),
-                           dtype=dtype, device=self.device)
+                           dtype=_FP8 if self.quantized else dtype, device=self.device)
         self.k = [self._pool[0, i] for i in range(self.num_layers)]
         self.v = [self._pool[1, i] for i in range(self.num_layers)]
+        if self.quantized:  # always zero: a slot never written dequantises to 0
+            self._scale_pool = torch.zeros((2, self.num_layers, self.num_blocks, block_size, self.num_kv_heads),
+                                           dtype=torch.float32, device=self.device)
+            self.k_scale = [self._scale_pool[0, i] for i in range(self.num_layers)]
+            self.v_scale = [self._scale_pool[1, i] for i in range(self.num_layers)]
         self.lens = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
         self.block_table = torch.full((self.batch, self.max_blocks), -1, dtype=torch.int32, device=self.device)
         # host state
@@ -85,6 +97,16 @@ class PagedKVCache:
         if self._bound is None:
             self._bound = max(self._lens)
         return self._bound
+
+    @property
+    def quantized(self) -> bool:
+        return self.kv_dtype is not None
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of key / value storage: the pool plus, when quantised, the scales."""
+        ts = [self._pool] + ([self._scale_pool] if self.quantized else [])
+        return sum(t.numel() * t.element_size() for t in ts)
 
     def _changed(self):
         """The lengths or the ownership changed: drop what was derived from them."""
@@ -297,17 +319,27 @@ class PagedKVCache:
     # ------------------------------------------------------------------ reference view
     def gather(self, layer: int):
         """(k, v) of ``layer`` as ``[B, max_len, Hk, D]``, zeros where no block is assigned
-        (plain torch over the device table; what the reference paths and the tests read)."""
+        (plain torch over the device table; what the reference paths and the tests read).
+        A quantised cache returns the dequantised values in ``dtype``."""
         t = self.block_table.long()
         ok = (t >= 0) & (t < self.num_blocks)
         idx = torch.where(ok, t, torch.zeros_like(t))
         outs = []
-        for pool in (self.k[layer], self.v[layer]):
-            g = pool[idx]  # [B, max_blocks, bs, Hk, D]
+        for n, pool in enumerate((self.k[layer], self.v[layer])):
+            if self.quantized:  # bytes: indexing is not defined on fp8
+                scales = (self.k_scale, self.v_scale)[n][layer]
+                g = dequantize_kv_fp8(pool.view(torch.uint8)[idx].view(_FP8), scales[idx], self.dtype)
+            else:
+                g = pool[idx]  # [B, max_blocks, bs, Hk, D]
             g = torch.where(ok[:, :, None, None, None], g, torch.zeros((), dtype=g.dtype, device=g.device))
             outs.append(g.reshape(self.batch, self.max_blocks * self.block_size, self.num_kv_heads,
                                   self.head_dim)[:, :self.max_len])
         return outs[0], outs[1]
+
+    def dequant(self, layer: int):
+        """(k, v) of ``layer`` as ``[B, max_len, Hk, D]`` in ``dtype``, through the table: what
+        ``gather`` returns."""
+        return self.gather(layer)
 
 
 # ---------------------------------------------------------------------- kv_append
@@ -329,10 +361,21 @@ def _kv_append_paged_ref(q4, cache, layer, Hq, Hk, cos, sin, rows_t):
     blk = cache.block_table.long()[crow.unsqueeze(1).expand(B, T), bidx]
     ok = ok & (blk >= 0) & (blk < cache.num_blocks)
     slot = (blk * bs + positions % bs)[ok]  # dropped tokens leave no slot
-    D = cache.head_dim
-    cache.k[layer].view(-1, Hk, D)[slot] = k[ok].to(cache.dtype)
-    cache.v[layer].view(-1, Hk, D)[slot] = v[ok].to(cache.dtype)
+    _D._store_slots(_FlatPool(cache), layer, slot, k[ok].to(cache.dtype), v[ok].to(cache.dtype))
     return q.contiguous()
+
+
+class _FlatPool:
+    """A paged cache's storage as [num_blocks * block_size, Hk, ...] views, for ``_store_slots``."""
+
+    def __init__(self, cache):
+        Hk, D = cache.num_kv_heads, cache.head_dim
+        self.quantized = cache.quantized
+        self.k = [t.view(-1, Hk, D) for t in cache.k]
+        self.v = [t.view(-1, Hk, D) for t in cache.v]
+        if cache.quantized:
+            self.k_scale = [t.view(-1, Hk) for t in cache.k_scale]
+            self.v_scale = [t.view(-1, Hk) for t in cache.v_scale]
 
 
 def kv_append_paged(qkv, cache: PagedKVCache, layer, Hq, Hk, cos, sin, rows):
@@ -362,6 +405,13 @@ def kv_append_paged(qkv, cache: PagedKVCache, layer, Hq, Hk, cos, sin, rows):
     if not _D._append_kernel_ok(q4, cache, cos, sin):
         return _kv_append_paged_ref(q4, cache, layer, Hq, Hk, cos, sin, rows_t)
     q = torch.empty(B, T, Hq, D, dtype=qkv.dtype, device=qkv.device)
+    if cache.quantized:
+        N.call("pa_kv_append_paged_f8", N.ptr(q4), ctypes_long_array(_fa_strides(q4)), N.ptr(cache.lens),
+               N.ptr(rows_t), N.ptr(cos), N.ptr(sin), int(cos.shape[0]) if cos is not None else 0,
+               N.ptr(cache.k[layer]), N.ptr(cache.v[layer]), N.ptr(cache.k_scale[layer]), N.ptr(cache.v_scale[layer]),
+               N.ptr(cache.block_table), cache.max_blocks, cache.num_blocks, cache.block_size, cache.max_len, N.ptr(q),
+               B, cache.batch, T, Hq, Hk, D, N.stream())
+        return q
     N.call("pa_kv_append_paged", N.ptr(q4), ctypes_long_array(_fa_strides(q4)), N.ptr(cache.lens), N.ptr(rows_t),
            N.ptr(cos), N.ptr(sin), int(cos.shape[0]) if cos is not None else 0, N.ptr(cache.k[layer]),
            N.ptr(cache.v[layer]), N.ptr(cache.block_table), cache.max_blocks, cache.num_blocks, cache.block_size,
@@ -379,8 +429,18 @@ def decode_attention_paged(q, cache: PagedKVCache, layer, scale, num_splits, kv_
             and _D._aligned16(q) and kv_len.is_cuda and kv_len.dtype == torch.int32 and kv_len.is_contiguous():
         ns = _D.default_num_splits(B, Hk, S_max) if num_splits is None else int(num_splits)
         qst = ctypes_long_array([q.stride(0), q.stride(2)])
-        if N.lib().pa_attn_decode_paged_ok(B, S_max, Hq, Hk, D, ns, qst, cache.block_size, cache.max_blocks,
-                                           cache.num_blocks):
+        if cache.quantized:
+            if N.lib().pa_attn_decode_paged_f8_ok(B, S_max, Hq, Hk, D, ns, qst, cache.block_size, cache.max_blocks,
+                                                  cache.num_blocks):
+                o = torch.empty(B, 1, Hq, D, dtype=q.dtype, device=q.device)
+                ws = torch.empty(B * Hq * ns * (D + 2), dtype=torch.float32, device=q.device)
+                N.call("pa_attn_decode_paged_f8", N.ptr(q), qst, N.ptr(cache.k[layer]), N.ptr(cache.v[layer]),
+                       N.ptr(cache.k_scale[layer]), N.ptr(cache.v_scale[layer]), N.ptr(cache.block_table),
+                       cache.max_blocks, cache.num_blocks, cache.block_size, N.ptr(kv_len), N.ptr(o), N.ptr(ws),
+                       B, S_max, Hq, Hk, D, float(scale), ns, N.stream())
+                return o
+        elif N.lib().pa_attn_decode_paged_ok(B, S_max, Hq, Hk, D, ns, qst, cache.block_size, cache.max_blocks,
+                                             cache.num_blocks):
             o = torch.empty(B, 1, Hq, D, dtype=q.dtype, device=q.device)
             ws = torch.empty(B * Hq * ns * (D + 2), dtype=torch.float32, device=q.device)
             N.call("pa_attn_decode_paged", N.ptr(q), qst, N.ptr(cache.k[layer]), N.ptr(cache.v[layer]),
