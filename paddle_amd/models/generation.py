@@ -18,6 +18,16 @@ Cache layout: see :mod:`paddle_amd.ops.decode` (one slab per layer, the default)
 row's first decoded token overwrites the first padding slot of a short prompt: positions
 are per row (``cache.lens``).
 
+``extend`` feeds T more tokens per row on top of a filled cache -- a further turn, a chunk of
+a long prompt, T candidates to score -- through a third hook,
+
+  ``_extend_hidden(input_ids, cache)``   T new tokens per row at the row's own positions
+        -> hidden states [B, T, H]: per layer norm -> QKV -> ``ops.kv_append`` ->
+        ``ops.extend_attention`` (``csrc/kernels/attn_extend.hip``) -> the rest,
+
+followed by one ragged ``cache.advance_each``.  ``prefill(chunk=C)`` /
+``generate(prefill_chunk=C)`` run a prompt C columns at a time on it.
+
 ``generate(graph=True)`` samples with the device kernel of :mod:`paddle_amd.ops.sampling`
 and replays one captured decode step (:class:`DecodeGraph`: step, sampler and ``advance``
 in one HIP graph) instead of launching it from Python every token.
@@ -291,7 +301,7 @@ class GenerationMixin:
         return KVCache(cfg.num_hidden_layers, batch, max_len, kvh, cfg.head_dim, p.dtype, p.device, kv_dtype=kv_dtype)
 
     @torch.no_grad()
-    def prefill(self, input_ids, cache, prompt_lens=None, rows=None):
+    def prefill(self, input_ids, cache, prompt_lens=None, rows=None, chunk=None):
         """Run the right-padded prompt [B, S] through the model, fill ``cache`` and return
         the logits [B, V] of each row's last valid position (``prompt_lens[b] - 1``;
         default: every row has S tokens).
@@ -301,28 +311,139 @@ class GenerationMixin:
         beyond it is dropped.  With ``rows`` (paged only) ``input_ids`` is
         ``[len(rows), S]``: those cache rows are freed, reserved and refilled and every
         other row keeps its blocks, its length and its tokens; the logits are
-        ``[len(rows), V]``."""
+        ``[len(rows), V]``.
+
+        ``chunk=C`` bounds the activations to C columns at a time: the first ``min(C, S)``
+        columns run the one-shot kernels, every further slice of C columns the ``extend``
+        path (``ops.kv_append`` + ``ops.extend_attention``) on top of the columns already
+        cached.  ``chunk >= S`` is the one-shot call, bit for bit; a smaller chunk computes
+        the same function in another summation order.  One difference: with an fp8 cache
+        later chunks attend to the *quantised* earlier chunks, one-shot prefill to the
+        unquantised prompt.  With quantised weights every chunk of more than
+        ``ops.skinny.MAX_ROWS`` rows pays one dequantisation per matrix."""
         self._check_generation_supported()
         B, S = input_ids.shape
         paged = getattr(cache, "paged", False)
         if rows is not None and not paged:
             raise ValueError("prefill: rows= needs a paged cache")
+        if chunk is not None:
+            chunk = int(chunk)
+            if chunk < 1:
+                raise ValueError(f"prefill: chunk must be at least 1, got {chunk}")
+            if chunk >= S:
+                chunk = None
         lens = [S] * B if prompt_lens is None else [int(x) for x in (
             prompt_lens.tolist() if torch.is_tensor(prompt_lens) else prompt_lens)]
         if len(lens) != B or min(lens) < 1 or max(lens) > S:
             raise ValueError(f"prompt_lens must be {B} values in [1, {S}], got {lens}")
         if paged:
-            y = self._prefill_paged(input_ids, cache, lens, rows)
-        else:
+            y = self._prefill_paged(input_ids, cache, lens, rows, chunk)
+        elif chunk is None:
             cache.reset()
             cache.check_room(S)
             y = self._prefill_hidden(input_ids, cache)
             cache.set_lens(lens)
+        else:
+            cache.reset()
+            cache.check_room(S)
+            y = self._prefill_chunks(input_ids, cache, lens, None, chunk)
+        if chunk is not None:
+            return self._lm_logits(y)  # [B, H]: each row's last valid position already
         H = y.shape[-1]
         last = torch.tensor([b * S + n - 1 for b, n in enumerate(lens)], dtype=torch.long, device=y.device)
         return self._lm_logits(ops.row_gather(y.reshape(B * S, H), last))
 
-    def _prefill_paged(self, input_ids, cache, lens, rows):
+    def _prefill_chunks(self, input_ids, cache, lens, rows, chunk):
+        """The prompt in slices of ``chunk`` columns (the cache is empty and, when paged,
+        reserved and inside ``prefilling(rows)``): the first slice through the one-shot
+        kernels, the others through the extend path.  After a slice row b has
+        ``min(columns so far, lens[b])`` tokens, so a finished row's padding lands behind
+        its own tokens (where the next decode step overwrites it, or in no block at all)
+        and never on them.  Returns the hidden state [B, H] of each row's last valid token."""
+        B, S = input_ids.shape
+        dev = input_ids.device
+        last_h = None
+        for c0 in range(0, S, chunk):
+            c1 = min(c0 + chunk, S)
+            ids = input_ids[:, c0:c1]
+            if c0 == 0:
+                y = self._prefill_hidden(ids, cache)
+                if rows is None:
+                    cache.set_lens([min(c1, n) for n in lens])
+                else:
+                    cache.set_lens([min(c1, n) for n in lens], rows)
+            else:
+                y = self._extend_hidden(ids, cache)
+                inc = [min(max(n - c0, 0), c1 - c0) for n in lens]
+                if rows is None:
+                    cache.advance_each(inc)
+                else:
+                    cache.advance_each(inc, rows)
+            # the rows whose last valid token is in this slice
+            here = [c0 <= n - 1 < c1 for n in lens]
+            if any(here):
+                idx = torch.tensor([b * (c1 - c0) + (n - 1 - c0 if h else 0) for b, (n, h) in enumerate(zip(lens, here))],
+                                   dtype=torch.long, device=dev)
+                got = ops.row_gather(y.reshape(B * (c1 - c0), y.shape[-1]), idx)
+                if last_h is None:  # a row not in this slice is in a later one and is replaced there
+                    last_h = got
+                else:
+                    last_h = torch.where(torch.tensor(here, device=dev).view(B, 1), got, last_h)
+        return last_h
+
+    @torch.no_grad()
+    def extend(self, input_ids, cache, new_lens=None, all_logits=False, rows=None):
+        """Feed T more tokens per row, ``input_ids`` [B, T] right-padded with ``new_lens[b]``
+        in [1, T] valid ones (default T), on top of what ``cache`` holds: a further turn of a
+        conversation, a chunk of a long prompt, or T candidate tokens to score in one pass.
+        Row b's tokens go in at its own positions ``lens[b] + t`` and attend to the row's
+        cached tokens plus the chunk itself up to t; afterwards ``lens[b] += new_lens[b]``.
+
+        Returns the logits [B, V] at each row's last valid new token, or with ``all_logits``
+        [B, T, V] (positions ``t >= new_lens[b]`` are unspecified).  ``rows`` (paged only):
+        ``input_ids`` is ``[len(rows), T]`` and every other cache row is untouched.
+
+        Overflow of ``max_len`` (a contiguous cache: the conservative ``bound + T``, since the
+        padding of a short row is written too; a paged one: each row's ``lens[b] +
+        new_lens[b]``, and the pool), of the rotary table or of ``max_position_embeddings``
+        raises ``ValueError`` on the host before any launch, with nothing changed."""
+        self._check_generation_supported()
+        B, T = input_ids.shape
+        paged = getattr(cache, "paged", False)
+        if rows is not None and not paged:
+            raise ValueError("extend: rows= needs a paged cache")
+        nl = [T] * B if new_lens is None else [int(x) for x in (
+            new_lens.tolist() if torch.is_tensor(new_lens) else new_lens)]
+        if T < 1 or len(nl) != B or min(nl) < 1 or max(nl) > T:
+            raise ValueError(f"new_lens must be {B} values in [1, {T}], got {nl}")
+        if paged:
+            rl = cache._check_rows(rows)
+            if len(rl) != B:
+                raise ValueError(f"extend: {B} rows of tokens for cache rows {rl}")
+            top = max(cache.host_lens[r] for r in rl) + T
+        else:
+            if B != cache.batch:
+                raise ValueError(f"extend: {B} rows of tokens for a cache of {cache.batch} rows")
+            top = cache.bound + T
+        if top > self._max_positions():
+            raise ValueError(f"extend: position {top - 1} is beyond the model's {self._max_positions()} positions")
+        if paged:
+            # each row's own new length, not lens + T: padding past a row's blocks is dropped
+            cache.reserve([cache.host_lens[r] + n for r, n in zip(rl, nl)], rl)
+            with cache.prefilling(rl):
+                y = self._extend_hidden(input_ids, cache)
+            cache.advance_each(nl, rl)
+        else:
+            cache.check_room(T)
+            y = self._extend_hidden(input_ids, cache)
+            cache.advance_each(nl)
+        H = y.shape[-1]
+        if all_logits:
+            return self._lm_logits(y.reshape(B * T, H)).view(B, T, -1)
+        last = torch.tensor([b * T + n - 1 for b, n in enumerate(nl)], dtype=torch.long, device=y.device)
+        return self._lm_logits(ops.row_gather(y.reshape(B * T, H), last))
+
+    def _prefill_paged(self, input_ids, cache, lens, rows, chunk=None):
         B, S = input_ids.shape
         if S > cache.max_len:
             raise ValueError(f"KV cache overflow: a prompt of {S} tokens > max_len {cache.max_len}")
@@ -340,6 +461,9 @@ class GenerationMixin:
                 raise ValueError(f"paged KV cache: out of blocks for prompts of {lens} tokens in rows {rows}")
             cache.free_rows(rows)
         cache.reserve(lens, rows)
+        if chunk is not None:  # the lengths move slice by slice and end at lens
+            with cache.prefilling(rows):
+                return self._prefill_chunks(input_ids, cache, lens, rows, chunk)
         with cache.prefilling(rows):
             y = self._prefill_hidden(input_ids, cache)
         cache.set_lens(lens, rows)
@@ -366,7 +490,7 @@ class GenerationMixin:
     @torch.no_grad()
     def generate(self, input_ids, max_new_tokens, prompt_lens=None, do_sample=False, temperature=1.0, top_k=0,
                  top_p=1.0, eos_token_id=None, pad_token_id=0, seed=None, cache="contiguous", block_size=None,
-                 graph=False, sampler=None, kv_dtype=None):
+                 graph=False, sampler=None, kv_dtype=None, prefill_chunk=None):
         """Generate ``max_new_tokens`` tokens after the right-padded prompts ``input_ids``
         [B, S] (``prompt_lens``: valid length per row, default S).
 
@@ -382,6 +506,9 @@ class GenerationMixin:
         ``kv_dtype="fp8_e4m3"`` keeps either cache in e4m3 with one scale per (token, kv
         head): half the bytes, and the tokens of a run whose cache holds the dequantised
         values (ops/kv_fp8.py).  Prefill attends to the unquantised prompt.
+
+        ``prefill_chunk=C`` runs the prompt through ``prefill(chunk=C)``: C columns at a time,
+        everything after the prefill unchanged.
 
         ``sampler``: ``"torch"`` (``sample_next`` with a ``torch.Generator``; the default) or
         ``"philox"`` (``ops.sample_step``: the device kernel, the counter-based generator and
@@ -429,7 +556,7 @@ class GenerationMixin:
             seed = int.from_bytes(os.urandom(8), "little") if seed is None else int(seed)
             how = (seed, do_sample, temperature, top_k, top_p)
             st = ops.SamplerState(B, max_new_tokens, dev, eos_token_id, pad_token_id)
-            ops.sample_step(self.prefill(input_ids, cache, prompt_lens), st, *how)
+            ops.sample_step(self.prefill(input_ids, cache, prompt_lens, chunk=prefill_chunk), st, *how)
             if max_new_tokens > 1 and graph:
                 g = self.decode_graph(cache, st, max_new_tokens, *how)
                 for _ in range(max_new_tokens - 1):
@@ -441,7 +568,7 @@ class GenerationMixin:
         out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=torch.long, device=dev)
         lengths = torch.full((B,), max_new_tokens, dtype=torch.long, device=dev)
         done = torch.zeros(B, dtype=torch.bool, device=dev)
-        logits = self.prefill(input_ids, cache, prompt_lens)
+        logits = self.prefill(input_ids, cache, prompt_lens, chunk=prefill_chunk)
         for step in range(max_new_tokens):
             nxt = sample_next(logits, do_sample, temperature, top_k, top_p, gen)
             nxt = torch.where(done, torch.full_like(nxt, int(pad_token_id)), nxt)

@@ -122,10 +122,11 @@ class GPTDecoderLayer(Layer):
         m = self._row_linear(m, self.fc2_w, self.fc2_b)
         return m, h2
 
-    def forward_cached(self, x, residual, cache, layer_idx, prefill):
+    def forward_cached(self, x, residual, cache, layer_idx, prefill, extend=False):
         """``forward`` for inference with a KV cache (no tensor parallelism): the whole
         prompt through the training kernels with its k / v stored at position 0
-        (prefill), or x [B, 1, H], one token per row against the cache (decode)."""
+        (prefill), x [B, 1, H], one token per row against the cache (decode), or x
+        [B, T, H], T tokens per row appended and attended with ``ops.extend_attention``."""
         eps = self.cfg.layer_norm_eps
         if residual is None:
             h = x
@@ -136,10 +137,18 @@ class GPTDecoderLayer(Layer):
             qkv_w = dense_weight(self.qkv_w, y)
             packed, a = prefill_qkv_attention(y, qkv_w, self.qkv_b, None, None, self.nh, self.nh)
             ops.kv_append(packed, cache, layer_idx, self.nh, self.nh)
+        elif extend and x.shape[0] * x.shape[1] > ops.skinny.MAX_ROWS:
+            # extend, many rows: the prefill products around append + extend attention
+            qkv = ops.linear(y, dense_weight(self.qkv_w, y), self.qkv_b)
+            q = ops.kv_append(qkv, cache, layer_idx, self.nh, self.nh)
+            a = ops.extend_attention(q, cache, layer_idx).view(x.shape[0], x.shape[1], -1)
         else:
             # decode: M = B rows per product, weight-streaming kernels (ops/skinny.py)
             q = ops.kv_append(ops.skinny_linear(y, self.qkv_w, self.qkv_b), cache, layer_idx, self.nh, self.nh)
-            a = ops.decode_attention(q, cache, layer_idx).view(x.shape[0], 1, -1)
+            if extend:  # T tokens per row at the row's own positions
+                a = ops.extend_attention(q, cache, layer_idx).view(x.shape[0], x.shape[1], -1)
+            else:
+                a = ops.decode_attention(q, cache, layer_idx).view(x.shape[0], 1, -1)
             a = ops.skinny_linear(a, self.out_w, self.out_b)
             y2, h2 = ops.layer_norm(a, self.ln2_w, self.ln2_b, eps, residual=h)
             m = ops.skinny_linear(y2, self.fc1_w, self.fc1_b, act="gelu_tanh")
@@ -215,10 +224,10 @@ class GPTForCausalLM(Layer, GenerationMixin):
         return ops.softmax_cross_entropy(logits, labels, inplace_grad=True)
 
     # ---- generation hooks (models/generation.py)
-    def _cached_hidden(self, x, cache, prefill):
+    def _cached_hidden(self, x, cache, prefill, extend=False):
         residual = None
         for i, layer in enumerate(self.layers):
-            x, residual = layer.forward_cached(x, residual, cache, i, prefill)
+            x, residual = layer.forward_cached(x, residual, cache, i, prefill, extend)
         y, _ = ops.layer_norm(x, self.ln_f_w, self.ln_f_b, self.cfg.layer_norm_eps, residual=residual)
         return y
 
@@ -228,6 +237,16 @@ class GPTForCausalLM(Layer, GenerationMixin):
     def _decode_hidden(self, tokens, cache):
         # learned positions gathered at each row's own length
         return self._cached_hidden(self.embeddings(tokens, position_ids=cache.lens.view(-1, 1)), cache, False)
+
+    def _extend_hidden(self, input_ids, cache):
+        # learned positions gathered at lens[:, None] + arange(T), of the rows the chunk goes to
+        rows_t = getattr(cache, "_prefill_rows", None)
+        lens = cache.lens if rows_t is None else cache.lens.index_select(0, rows_t.long())
+        pos = lens.long().view(-1, 1) + torch.arange(input_ids.shape[1], device=lens.device)
+        return self._cached_hidden(self.embeddings(input_ids, position_ids=pos), cache, False, True)
+
+    def _max_positions(self):
+        return self.cfg.max_position_embeddings
 
     def _lm_logits(self, y):
         return ops.skinny_linear_t(y, self.embeddings.word_embeddings)

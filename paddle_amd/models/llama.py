@@ -171,11 +171,14 @@ class LlamaDecoderLayer(Layer):
         hm = ops.swiglu(ops.linear(y2, dense_weight(self.gate_up_proj, y2)))
         return ops.linear(hm, dense_weight(self.down_proj, hm))
 
-    def forward_cached(self, x, residual, cos, sin, cache, layer_idx, prefill):
+    def forward_cached(self, x, residual, cos, sin, cache, layer_idx, prefill, extend=False):
         """``forward`` for inference with a KV cache (no tensor parallelism).  Prefill: the
         whole prompt through the training kernels, its rotated k / v stored at position
         0.  Decode: x [B, 1, H], one token per row appended and rotated at the row's own
-        position, then split-KV attention over the cache."""
+        position, then split-KV attention over the cache.  Extend: x [B, T, H], T tokens per
+        row appended at the row's own positions, then ``ops.extend_attention``; the weight
+        products are the decode ones up to ``ops.skinny.MAX_ROWS`` rows and the prefill ones
+        above."""
         eps = self.cfg.rms_norm_eps
         if residual is None:
             h = x
@@ -186,10 +189,17 @@ class LlamaDecoderLayer(Layer):
             qkv_w = dense_weight(self.qkv_proj, y)
             packed, a = prefill_qkv_attention(y, qkv_w, None, cos, sin, self.nh, self.nkv)
             ops.kv_append(packed, cache, layer_idx, self.nh, self.nkv)
+        elif extend and x.shape[0] * x.shape[1] > ops.skinny.MAX_ROWS:
+            qkv = ops.linear(y, dense_weight(self.qkv_proj, y))
+            q = ops.kv_append(qkv, cache, layer_idx, self.nh, self.nkv, cos, sin)
+            a = ops.extend_attention(q, cache, layer_idx).view(x.shape[0], x.shape[1], -1)
         else:
             # decode: M = B rows per product, weight-streaming kernels (ops/skinny.py)
             q = ops.kv_append(ops.skinny_linear(y, self.qkv_proj), cache, layer_idx, self.nh, self.nkv, cos, sin)
-            a = ops.decode_attention(q, cache, layer_idx).view(x.shape[0], 1, -1)
+            if extend:
+                a = ops.extend_attention(q, cache, layer_idx).view(x.shape[0], x.shape[1], -1)
+            else:
+                a = ops.decode_attention(q, cache, layer_idx).view(x.shape[0], 1, -1)
             a = ops.skinny_linear(a, self.o_proj)
             y2, h2 = ops.rms_norm(a, self.post_attention_layernorm, eps, residual=h)
             if self.mlp_interleaved:
@@ -276,13 +286,19 @@ class LlamaForCausalLM(Layer, GenerationMixin):
         return self.logits_and_loss(self.hidden_states(input_ids), labels)
 
     # ---- generation hooks (models/generation.py)
-    def _cached_hidden(self, input_ids, cache, prefill):
+    def _cached_hidden(self, input_ids, cache, prefill, extend=False):
         x = self.embed(input_ids)
         residual = None
         for i, layer in enumerate(self.layers):
-            x, residual = layer.forward_cached(x, residual, self.rope_cos, self.rope_sin, cache, i, prefill)
+            x, residual = layer.forward_cached(x, residual, self.rope_cos, self.rope_sin, cache, i, prefill, extend)
         y, _ = ops.rms_norm(x, self.norm, self.cfg.rms_norm_eps, residual=residual)
         return y
+
+    def _extend_hidden(self, input_ids, cache):
+        return self._cached_hidden(input_ids, cache, False, True)
+
+    def _max_positions(self):
+        return self.rope_cos.shape[0]
 
     def _prefill_hidden(self, input_ids, cache):
         return self._cached_hidden(input_ids, cache, True)

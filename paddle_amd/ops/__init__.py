@@ -6,6 +6,7 @@ from .fused import (apply_rotary, embedding, flash_attention, flash_attention_va
                     position_add, mean_valid, cross_entropy_tokens, reshape, stack_mean,
                     row_gather, concat_rows)
 from .decode import KVCache, PagedKVCache, kv_append, decode_attention  # noqa: F401
+from .decode import extend_attention, default_extend_splits  # noqa: F401
 from .kv_fp8 import quantize_kv_fp8, dequantize_kv_fp8  # noqa: F401
 from . import skinny  # noqa: F401
 from .skinny import skinny_ok, skinny_linear, skinny_linear_t, skinny_default_splits  # noqa: F401

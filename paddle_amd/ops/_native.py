@@ -68,6 +68,11 @@ _SIGS = {
     "pa_flash_attn_fwd": [_P, _P, _P, _P, _P, _LP, _I, _I, _I, _I, _I, _I, _F, _I, _P],
     "pa_kv_append": [_P, _LP, _P, _P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
     "pa_i32_add": [_P, _I, _I, _P],
+    "pa_i32_add_rows": [_P, _P, _I, _P],
+    "pa_attn_extend_ok": [_I, _I, _I, _I, _I, _I, _I, _LP, _I, _I, _I],
+    "pa_attn_extend_splits": [_I, _I, _I, _I],
+    "pa_attn_extend": [_P, _LP, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _I,
+                       _P],
     "pa_attn_decode_ok": [_I, _I, _I, _I, _I, _I, _LP],
     "pa_attn_decode_splits": [_I, _I, _I],
     "pa_attn_decode": [_P, _LP, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],

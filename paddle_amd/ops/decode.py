@@ -1,6 +1,8 @@
-"""KV-cache decode ops: the cache object, ``kv_append`` and ``decode_attention``.
+"""KV-cache decode ops: the cache object, ``kv_append``, ``decode_attention`` (one new token
+per row) and ``extend_attention`` (T new tokens per row, causal inside the chunk).
 
-GPU bf16 tensors run the gfx950 kernels of ``csrc/kernels/attn_decode.hip``; CPU
+GPU bf16 tensors run the gfx950 kernels of ``csrc/kernels/attn_decode.hip`` (and
+``csrc/kernels/attn_extend.hip``: the MFMA kernel behind ``extend_attention``); CPU
 tensors, other dtypes and shapes the kernels do not cover run the plain-torch
 definitions below (the fp32 oracle of the GPU tests).  These are inference ops: they
 record nothing on the tape and run under ``torch.no_grad()``.
@@ -30,7 +32,8 @@ from . import _native as N
 from .fused import _attn_ref, _check_scale, _fa_strides, ctypes_long_array
 from .kv_fp8 import _FP8, check_kv_dtype, dequantize_kv_fp8, quantize_kv_fp8
 
-__all__ = ["KVCache", "PagedKVCache", "kv_append", "decode_attention"]
+__all__ = ["KVCache", "PagedKVCache", "kv_append", "decode_attention", "extend_attention",
+           "default_extend_splits"]
 
 
 class KVCache:
@@ -112,6 +115,18 @@ class KVCache:
             self.lens += int(T)
         self._bound += int(T)
 
+    def advance_each(self, new_lens):
+        """lens[b] += new_lens[b] from a host list: the ragged advance after a right-padded
+        chunk (no device read).  The host bound moves by the largest count; it raises when
+        ``bound + max(new_lens)`` passes ``max_len`` -- the rule of ``check_room``, because the
+        padding tokens of a short row are written too (and later overwritten)."""
+        host = [int(x) for x in (new_lens.tolist() if torch.is_tensor(new_lens) else new_lens)]
+        if len(host) != self.batch or min(host) < 0:
+            raise ValueError(f"advance_each: need {self.batch} counts >= 0, got {host}")
+        self.check_room(max(host))
+        _add_rows(self.lens, host)
+        self._bound += max(host)
+
     def set_lens(self, lens):
         """lens = the given per-row lengths (host list or tensor), e.g. the prompt lengths
         after a right-padded prefill; the host bound becomes their maximum."""
@@ -120,6 +135,21 @@ class KVCache:
             raise ValueError(f"set_lens: need {self.batch} lengths in [0, {self.max_len}], got {host}")
         self.lens.copy_(torch.tensor(host, dtype=torch.int32))
         self._bound = max(host)
+
+
+def _add_rows(lens, host):
+    """lens (int32, device or CPU) += the host list, on the current stream without a
+    synchronising call (the staging buffer comes from torch's caching host allocator, which
+    does not hand it out again before the copy has finished)."""
+    inc = torch.tensor(host, dtype=torch.int32)
+    if not lens.is_cuda:
+        lens += inc
+        return
+    staging = torch.empty(inc.shape, dtype=torch.int32, pin_memory=True)
+    staging.copy_(inc)
+    dev = torch.empty_like(lens)
+    dev.copy_(staging, non_blocking=True)
+    N.call("pa_i32_add_rows", N.ptr(lens), N.ptr(dev), lens.numel(), N.stream())
 
 
 def _rope_at(x, cos, sin, positions):
@@ -288,6 +318,114 @@ def decode_attention(q, cache, layer: int, scale: float | None = None, num_split
             return o
     k, v = cache.dequant(layer)
     return _decode_attention_ref(q, k, v, kv_len, float(scale))
+
+
+def _extend_attention_ref(q, k, v, base_len, scale):
+    """fp32 attention of T query tokens per row over the cached keys: token t of row b sees
+    the keys n < min(max(base_len[b], 0) + t + 1, S_max) (``fused._attn_ref`` per row, causal
+    inside the chunk)."""
+    T, S_max = q.shape[1], k.shape[1]
+    outs = []
+    for b, n in enumerate(base_len.tolist()):
+        n = max(int(n), 0)
+        if n + T <= S_max:
+            outs.append(_attn_ref(q[b:b + 1], k[b:b + 1, :n + T], v[b:b + 1, :n + T], True, scale))
+        else:  # the end of the cache cuts the chunk: token by token
+            outs.append(torch.cat([_attn_ref(q[b:b + 1, t:t + 1], k[b:b + 1, :min(n + t + 1, S_max)],
+                                             v[b:b + 1, :min(n + t + 1, S_max)], False, scale)
+                                   for t in range(T)], 1))
+    return torch.cat(outs, 0)
+
+
+def default_extend_splits(batch: int, num_kv_heads: int, T: int, max_len: int) -> int:
+    """The split count ``extend_attention`` picks from the launch shape alone (never from the
+    lengths), for either cache layout."""
+    return int(N.lib().pa_attn_extend_splits(int(batch), int(num_kv_heads), int(T), int(max_len)))
+
+
+def _extend_kernel(q, cache, layer, scale, num_splits, base_len, rows_t, out=None):
+    """Launch pa_attn_extend when it takes the problem; None otherwise.  ``out``: a contiguous
+    [B, T, Hq, D] buffer to write (the tests border it with a sentinel)."""
+    B, T, Hq, D = q.shape
+    Hk, S_max = cache.num_kv_heads, cache.max_len
+    paged = getattr(cache, "paged", False)
+    if not (q.is_cuda and q.dtype == torch.bfloat16 and cache.dtype == torch.bfloat16 and q.stride(-1) == 1
+            and _aligned16(q) and base_len.is_cuda and base_len.dtype == torch.int32 and base_len.is_contiguous()
+            and Hk > 0 and Hq % Hk == 0):
+        return None
+    ns = default_extend_splits(B, Hk, T, S_max) if num_splits is None else int(num_splits)
+    qst = ctypes_long_array(_fa_strides(q))
+    geom = (cache.block_size, cache.max_blocks, cache.num_blocks) if paged else (0, 0, 0)
+    if not N.lib().pa_attn_extend_ok(B, T, S_max, Hq, Hk, D, ns, qst, *geom):
+        return None
+    o = torch.empty(B, T, Hq, D, dtype=q.dtype, device=q.device) if out is None else out
+    ws = torch.empty(B * T * Hq * ns * (D + 2), dtype=torch.float32, device=q.device) if ns > 1 else None
+    ksc = cache.k_scale[layer] if cache.quantized else None
+    vsc = cache.v_scale[layer] if cache.quantized else None
+    N.call("pa_attn_extend", N.ptr(q), qst, N.ptr(cache.k[layer]), N.ptr(cache.v[layer]), N.ptr(ksc), N.ptr(vsc),
+           N.ptr(cache.block_table) if paged else None, geom[1], geom[2], geom[0], N.ptr(rows_t), N.ptr(base_len),
+           N.ptr(o), N.ptr(ws), B, cache.batch, T, S_max, Hq, Hk, D, float(scale), ns, N.stream())
+    return o
+
+
+@torch.no_grad()
+def extend_attention(q, cache, layer: int, scale: float | None = None, num_splits: int | None = None,
+                     base_len=None, rows=None):
+    """Attention of T new tokens per row, q [B, T, Hq, D] (what ``kv_append`` returns), over
+    layer ``layer`` of either cache.  Token t of row b attends to the cached keys
+    ``n < min(max(base_len[b], 0) + t + 1, max_len)``: the row's earlier tokens plus the chunk
+    itself up to t.  The chunk is already in the cache -- ``kv_append`` ran first and the
+    lengths have not advanced -- so ``base_len`` defaults to ``cache.lens``.  Returns o
+    [B, T, Hq, D].
+
+    ``rows`` (paged cache only, the rule and the error of ``kv_append``): q row i reads cache
+    row ``rows[i]``; inside ``cache.prefilling(rows)`` the mapping comes from the scope.  An
+    explicit ``base_len`` is indexed by q row.
+
+    On the GPU (bf16 q, D in {64, 128}, Hq/Hk in {1, 2, 4, 8}) this is ``pa_attn_extend`` of
+    ``csrc/kernels/attn_extend.hip``: both products on the bf16 MFMA, the key range cut into
+    ``num_splits`` ranges (``default_extend_splits``: from the launch shape only), bit-identical
+    from run to run.  The paged instantiation returns the bits of the contiguous one for equal
+    tokens, ``base_len`` and ``num_splits``; the e4m3 one the bits of the bf16 one over
+    ``cache.dequant(layer)``.  At T = 1 it is *not* bit-equal to ``decode_attention`` (different
+    arithmetic), and different chunkings of the same tokens are not bit-equal to each other.
+    CPU tensors, other dtypes, other shapes and a misaligned q run the plain-torch reference
+    over ``cache.dequant(layer)``."""
+    if q.dim() != 4:
+        raise ValueError(f"extend_attention: q must be [B, T, Hq, D], got {tuple(q.shape)}")
+    B, T, Hq, D = q.shape
+    paged = getattr(cache, "paged", False)
+    if rows is not None and not paged:
+        raise ValueError("extend_attention: rows= needs a paged cache (a contiguous cache has every row)")
+    rows_t = None
+    nrows = cache.batch
+    if paged:
+        if cache._in_prefill:
+            if rows is not None:
+                raise ValueError("extend_attention: rows= inside PagedKVCache.prefilling() (the scope maps the rows)")
+            rows_t = cache._prefill_rows
+        elif rows is not None:
+            rows_t = cache._index_tensor(cache._check_rows(rows))
+        if rows_t is not None:
+            nrows = rows_t.numel()
+    Hk = cache.num_kv_heads
+    if T < 1 or B != nrows or D != cache.head_dim or Hq % Hk:
+        raise ValueError(f"extend_attention: q {tuple(q.shape)} does not match the cache "
+                         f"({nrows} rows, Hk={Hk}, D={cache.head_dim})")
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    _check_scale(scale, "extend_attention")
+    if base_len is None:
+        base_len = cache.lens if rows_t is None else cache.lens.index_select(0, rows_t.long()).contiguous()
+    elif base_len.numel() != B:
+        raise ValueError(f"extend_attention: base_len has {base_len.numel()} entries for {B} q rows")
+    o = _extend_kernel(q, cache, layer, float(scale), num_splits, base_len, rows_t)
+    if o is not None:
+        return o
+    k, v = cache.dequant(layer)
+    if rows_t is not None:
+        k, v = k.index_select(0, rows_t.long()), v.index_select(0, rows_t.long())
+    return _extend_attention_ref(q, k, v, base_len, float(scale))
 
 
 from . import paged as _paged  # noqa: E402  (paged.py uses the helpers above)

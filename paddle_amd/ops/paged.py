@@ -261,6 +261,24 @@ class PagedKVCache:
         self._lens = [n + int(T) for n in self._lens]
         self._changed()
 
+    def advance_each(self, new_lens, rows=None):
+        """lens[b] += new_lens[b] from a host list, for every row or for ``rows`` only: the
+        ragged advance after a right-padded chunk (no device read).  Each row's
+        ``lens[b] + new_lens[b]`` is reserved first: when the pool (or ``max_len``) is short,
+        ``ValueError`` is raised before any launch and nothing has changed."""
+        rows = self._check_rows(rows)
+        host = _host_ints(new_lens)
+        if len(host) != len(rows) or min(host) < 0:
+            raise ValueError(f"advance_each: need {len(rows)} counts >= 0, got {host}")
+        self.reserve([self._lens[r] + n for r, n in zip(rows, host)], rows)
+        inc = [0] * self.batch
+        for r, n in zip(rows, host):
+            inc[r] = n
+        _D._add_rows(self.lens, inc)
+        for r, n in zip(rows, host):
+            self._lens[r] += n
+        self._changed()
+
     def set_lens(self, lens, rows=None):
         """lens = the given lengths (host list or tensor) for every row, or for ``rows``
         only.  Each row must already own the blocks for its length (``reserve``)."""
