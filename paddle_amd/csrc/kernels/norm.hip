@@ -330,6 +330,7 @@ using namespace pa;
 PA_EXPORT int pa_norm_fwd(int dtype, int rms, const void* x, const void* res, const void* w,
                           const void* b, void* y, void* hout, float* mean, float* rstd, long N,
                           int H, float eps, hipStream_t st) {
+  if (H <= 0 || H % 8 != 0) return (int)hipErrorInvalidValue;  // 8-element vectors: a tail would run past the row
   const int nv = (H + 511) / 512;
 #define PA_D(T)                                                                          \
   if (nv <= 1) return launch_fwd<T, 1>(rms, x, res, w, b, y, hout, mean, rstd, N, H, eps, st); \
@@ -342,10 +343,13 @@ PA_EXPORT int pa_norm_fwd(int dtype, int rms, const void* x, const void* res, co
   return (int)hipErrorInvalidValue;
 }
 
-// Workspace: ws must hold 2 * min(512, ceil(N/4)) * H floats.
+// Workspace: ws must hold 2 * G * H floats (dW partials, then dB partials) for the G blocks
+// launch_bwd picks: at most 1024, by default min(512, ceil(N/16)).  Callers size it for
+// min(1024, ceil(N/4)) blocks.
 PA_EXPORT int pa_norm_bwd(int dtype, int rms, const void* dy, const void* h, const void* w,
                           const float* mean, const float* rstd, const void* dres, void* dx,
                           void* dw, void* db, float* ws, long N, int H, hipStream_t st) {
+  if (H <= 0 || H % 8 != 0) return (int)hipErrorInvalidValue;
   const int nv = (H + 511) / 512;
 #define PA_D(T)                                                                                 \
   if (nv <= 1) return launch_bwd<T, 1>(rms, dy, h, w, mean, rstd, dres, dx, dw, db, ws, N, H, st); \

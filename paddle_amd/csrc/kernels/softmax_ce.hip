@@ -50,6 +50,9 @@ __device__ __forceinline__ MS row_ms(const T* __restrict__ x, int V) {
       float m = v[0];
 #pragma unroll
       for (int j = 1; j < 8; ++j) m = fmaxf(m, v[j]);
+      // a chunk of eight -inf (masked / padded columns) holds no mass: {-inf, 0}, not
+      // exp(-inf - -inf) = NaN
+      if (m == -INFINITY) continue;
       float s = 0.f;
 #pragma unroll
       for (int j = 0; j < 8; ++j) s += __expf(v[j] - m);

@@ -297,7 +297,7 @@ def layer_norm(ctx):
     eps = ctx.attr("epsilon")
     sc1 = sc.reshape(-1) if sc is not None else None
     b1 = b.reshape(-1).to(x2.dtype) if b is not None else None
-    if not ctx.meta and _fused.norm_kernel_ok(x2, sc1):
+    if not ctx.meta and _fused.norm_kernel_ok(x2, sc1, b1):
         # one HIP pass: Y plus the row statistics the grad op reads back
         y, mean, rstd = _fused.layer_norm_stats(x2, sc1, b1, eps)
         ctx.set_output("Y", y.reshape(x.shape))

@@ -151,9 +151,21 @@ def layer_norm_stats_grad(dy2, x2, w, mean, rstd, has_b):
     return dx, dw, db
 
 
-def norm_kernel_ok(x2, w):
-    return (x2.is_cuda and w is not None and x2.dtype in (torch.float32, torch.bfloat16) and w.dtype == x2.dtype
-            and x2.shape[-1] % 8 == 0 and x2.shape[-1] <= 8192 and x2.shape[0] > 0)
+def _on_gpu(t):
+    return t.is_cuda
+
+
+def norm_kernel_ok(x2, w, b=None, res=None):
+    """True when the norm kernel can take rows of ``x2`` [..., H]: fp32 / bf16 on the GPU,
+    H a multiple of 8 (the kernel moves 8-element vectors) and at most 8192 (16 vectors per
+    lane), and ``w`` / ``b`` / ``res`` in x2's dtype (the kernel reads them through x2's
+    element type).  Everything else runs :class:`_NormRefFn`."""
+    H = x2.shape[-1]
+    return (_on_gpu(x2) and w is not None and x2.dtype in (torch.float32, torch.bfloat16) and w.dtype == x2.dtype
+            and w.numel() == H and _on_gpu(w)
+            and (b is None or (b.dtype == x2.dtype and b.numel() == H and _on_gpu(b)))
+            and (res is None or (res.dtype == x2.dtype and res.shape == x2.shape and _on_gpu(res)))
+            and H % 8 == 0 and H <= 8192 and x2.numel() > 0)
 
 
 def param_ready(w):
@@ -205,7 +217,7 @@ def rms_norm(x, weight, eps=1e-6, residual=None):
     """y = x * rsqrt(mean(x^2) + eps) * weight.  With ``residual``: h = x + residual,
     returns (rms_norm(h), h) with the add fused into the same pass."""
     param_ready(weight)
-    if x.is_cuda:
+    if norm_kernel_ok(x, weight, None, residual):
         y, h = _tape.apply(_NormFn, x, residual, weight, None, eps, True)
         return (y, h) if residual is not None else y
     y, h = _tape.apply(_NormRefFn, x, residual, weight, None, eps, True)
@@ -217,7 +229,7 @@ def layer_norm(x, weight, bias=None, eps=1e-5, residual=None):
         param_ready(weight)
     if bias is not None:
         param_ready(bias)
-    if x.is_cuda and weight is not None and x.shape[-1] % 8 == 0 and x.shape[-1] <= 8192:
+    if norm_kernel_ok(x, weight, bias, residual):
         y, h = _tape.apply(_NormFn, x, residual, weight, bias, eps, False)
         return (y, h) if residual is not None else y
     if weight is None:
@@ -787,7 +799,9 @@ def swiglu(x, y=None):
     """silu(gate) * up.  With one argument, x = [gate | up] along the last axis."""
     if y is not None:
         x = torch.cat([x, y], -1)
-    if x.is_cuda and (x.shape[-1] // 2) % 8 == 0:
+    if x.shape[-1] % 2:
+        raise ValueError(f"swiglu: the last dimension holds [gate | up] and must be even, got {x.shape[-1]}")
+    if x.is_cuda and x.shape[-1] % 16 == 0:  # [gate | up] halves of whole 8-element vectors
         return _tape.apply(_SwiGLUFn, x)
     return _tape.apply(_SwiGLURefFn, x)
 
