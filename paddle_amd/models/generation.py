@@ -490,7 +490,7 @@ class GenerationMixin:
     @torch.no_grad()
     def generate(self, input_ids, max_new_tokens, prompt_lens=None, do_sample=False, temperature=1.0, top_k=0,
                  top_p=1.0, eos_token_id=None, pad_token_id=0, seed=None, cache="contiguous", block_size=None,
-                 graph=False, sampler=None, kv_dtype=None, prefill_chunk=None):
+                 graph=False, sampler=None, kv_dtype=None, prefill_chunk=None, draft=None, num_draft=4):
         """Generate ``max_new_tokens`` tokens after the right-padded prompts ``input_ids``
         [B, S] (``prompt_lens``: valid length per row, default S).
 
@@ -516,8 +516,24 @@ class GenerationMixin:
         random seed).  ``graph=True`` captures one decode step after the prefill and replays
         it for the remaining tokens (:class:`DecodeGraph`); it needs, and defaults to, the
         ``"philox"`` sampler.  Greedy tokens are the same on every path; sampled tokens differ
-        between the two samplers, which draw different random numbers."""
+        between the two samplers, which draw different random numbers.
+
+        ``draft=model`` turns on speculative decoding (models/speculative.py): the draft proposes
+        ``num_draft`` (1..16) tokens per row and round, this model scores them in one ``extend``
+        pass and ``ops.spec_verify`` keeps the longest accepted run plus one token of its own.
+        Greedy tokens are this model's greedy tokens, sampled tokens are distributed as its
+        filtered distribution.  The sampler is ``"philox"``; ``graph=True`` is not supported.
+        Both caches hold ``S + max_new_tokens + num_draft`` tokens; the decoder, with its
+        counters, stays at ``self.last_speculation``."""
         self._check_generation_supported()
+        if draft is not None:
+            from .speculative import SpeculativeDecoder
+
+            dec = SpeculativeDecoder(self, draft, num_draft)
+            self.last_speculation = dec
+            return dec.generate(input_ids, max_new_tokens, prompt_lens, do_sample, temperature, top_k, top_p,
+                                eos_token_id, pad_token_id, seed, cache, block_size, graph, sampler, kv_dtype,
+                                prefill_chunk)
         if sampler is None:
             sampler = "philox" if graph else "torch"
         if sampler not in ("torch", "philox"):

@@ -14,3 +14,5 @@ from . import skinny_fp8  # noqa: F401
 from .skinny_fp8 import Fp8Weight, quantize_weight_fp8, skinny_fp8_ok, skinny_fp8_default_splits  # noqa: F401
 from . import sampling  # noqa: F401
 from .sampling import SamplerState, philox_uniform, sample_step, sample_tokens  # noqa: F401
+from . import speculative  # noqa: F401
+from .speculative import SpecState, spec_commit, spec_judge, spec_kernel_ok, spec_margins, spec_verify  # noqa: F401

@@ -101,6 +101,10 @@ _SIGS = {
     "pa_sample_ok": [_I, _I, _I, _L, _P],
     "pa_philox_uniform": [ctypes.c_ulonglong, _P, _I, _P, _I, _P],
     "pa_sample": [_I, _P, _L, _I, _I, ctypes.c_ulonglong, _P, _I, _I, _F, _I, _F, _P, _P, _I, _P, _P, _L, _L, _P],
+    "pa_spec_judge_ok": [_I, _I, _I, _I, _P, _L, _L, _P, _L, _L, _I],
+    "pa_spec_judge": [_I, _P, _L, _L, _P, _L, _L, _P, _I, _I, _I, ctypes.c_ulonglong, _P, _I, _I, _F, _I, _F, _P, _P,
+                      _P],
+    "pa_spec_commit": [_P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _L, _L, _P],
     "pa_fa_bwd_set_variant": [_I],
     "pa_fa_fwd_set_variant": [_I],
     "pa_fa_bwd_get_variant": [],

@@ -127,6 +127,22 @@ class KVCache:
         _add_rows(self.lens, host)
         self._bound += max(host)
 
+    def rewind_each(self, counts, bound=None):
+        """lens[b] -= counts[b] from a host list (counts >= 0): take the last tokens of each row
+        back out, e.g. the rejected candidates of a speculative round (no device read).  The
+        host knows only an upper bound of ``lens``, so the caller passes the new exact maximum
+        as ``bound`` (it may only lower the bound); without it the bound stays where it is.
+        The slots beyond ``lens`` keep their stale contents: every kernel masks by ``lens``,
+        and the next append overwrites them."""
+        host = [int(x) for x in (counts.tolist() if torch.is_tensor(counts) else counts)]
+        if len(host) != self.batch or min(host) < 0 or max(host) > self._bound:
+            raise ValueError(f"rewind_each: need {self.batch} counts in [0, {self._bound}], got {host}")
+        if bound is not None and not 0 <= int(bound) <= self._bound:
+            raise ValueError(f"rewind_each: bound must be in [0, {self._bound}], got {bound}")
+        _add_rows(self.lens, [-n for n in host])
+        if bound is not None:
+            self._bound = int(bound)
+
     def set_lens(self, lens):
         """lens = the given per-row lengths (host list or tensor), e.g. the prompt lengths
         after a right-padded prefill; the host bound becomes their maximum."""

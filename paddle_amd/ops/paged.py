@@ -279,6 +279,28 @@ class PagedKVCache:
             self._lens[r] += n
         self._changed()
 
+    def rewind_each(self, counts, rows=None):
+        """lens[b] -= counts[b] from a host list (counts >= 0), for every row or for ``rows``
+        only: take the last tokens of a row back out, e.g. the rejected candidates of a
+        speculative round (no device read).  The rows keep their blocks (the next tokens
+        reuse them) and the table is neither touched nor uploaded; the slots beyond ``lens``
+        keep their stale contents, which every kernel masks by ``lens`` and the next append
+        overwrites.  A count above the row's length raises ``ValueError`` with nothing changed."""
+        rows = self._check_rows(rows)
+        host = _host_ints(counts)
+        if len(host) != len(rows) or min(host) < 0:
+            raise ValueError(f"rewind_each: need {len(rows)} counts >= 0, got {host}")
+        for r, n in zip(rows, host):
+            if n > self._lens[r]:
+                raise ValueError(f"rewind_each: row {r} holds {self._lens[r]} tokens, cannot take back {n}")
+        dec = [0] * self.batch
+        for r, n in zip(rows, host):
+            dec[r] = -n
+        _D._add_rows(self.lens, dec)
+        for r, n in zip(rows, host):
+            self._lens[r] -= n
+        self._changed()
+
     def set_lens(self, lens, rows=None):
         """lens = the given lengths (host list or tensor) for every row, or for ``rows``
         only.  Each row must already own the blocks for its length (``reserve``)."""

@@ -256,9 +256,12 @@ def sample_step(logits, st: SamplerState, seed=0, do_sample=False, temperature=1
     if logits.shape[0] != st.batch or logits.device != st.tok.device:
         raise ValueError(f"sample_step: logits {tuple(logits.shape)} on {logits.device} do not match the state "
                          f"(B={st.batch} on {st.tok.device})")
+    pos = getattr(st, "pos", None)  # an ops.SpecState counts the tokens written per row as well
     if sample_kernel_ok(logits):
         _launch(logits, seed, N.ptr(st.step), 0, do_sample, temperature, top_k, top_p, st.tok, st)
         N.call("pa_i32_add", N.ptr(st.step), 1, 1, N.stream())
+        if pos is not None:
+            N.call("pa_i32_add", N.ptr(pos), st.batch, 1, N.stream())
         return st.tok
     step = int(st.step)
     nxt = _reference_tokens(logits, seed, step, do_sample, temperature, top_k, top_p)
@@ -271,4 +274,6 @@ def sample_step(logits, st: SamplerState, seed=0, do_sample=False, temperature=1
         st.done |= hit
     st.tok.copy_(nxt)
     st.step += 1
+    if pos is not None:
+        pos += 1
     return st.tok
