@@ -188,6 +188,30 @@ class MoELayer(Layer):
         self.capacity_factor = capacity_factor
         self.sync_free = sync_free
         self.l_aux = None
+        self._stacked = None
+
+    @torch.no_grad()
+    def stacked_experts(self):
+        """The local experts' weights as two stacks ``(gate_up [n, H, 2I], down [n, I, H])``, what
+        ``ops.moe_decode_ffn`` streams.  Grouped experts: the parameters themselves.  A list of
+        per-expert layers (``gate_up`` / ``down`` parameters each) is stacked once and every
+        expert's ``.data`` is re-pointed at its slice of the stack, so nothing is held twice and
+        ``forward`` computes the same bits on the same numbers; later calls check two
+        ``data_ptr()``s (an optimizer or a ``load_state_dict`` that writes in place keeps the
+        slices, one that replaces ``.data`` makes the next call stack again)."""
+        if self.grouped:
+            return self.experts.gate_up, self.experts.down
+        ex = self.experts
+        st = self._stacked
+        if st is not None and ex[0].gate_up.data_ptr() == st[0].data_ptr() and ex[0].down.data_ptr() == st[1].data_ptr():
+            return st
+        gu = torch.stack([e.gate_up.data for e in ex])
+        dn = torch.stack([e.down.data for e in ex])
+        for i, e in enumerate(ex):
+            e.gate_up.data = gu[i]
+            e.down.data = dn[i]
+        self._stacked = (gu, dn)
+        return self._stacked
 
     def forward(self, x):
         from ...ops import fused as _F

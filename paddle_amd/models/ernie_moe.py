@@ -23,6 +23,7 @@ from ..nn import Layer
 from ..ops import grouped as _grouped
 from ..ops.fp8 import fp8_linear
 from ..ops.fused import param_ready
+from .generation import GenerationMixin, prefill_qkv_attention
 from .llama import _dt, _param
 
 
@@ -182,16 +183,78 @@ class ErnieMoEDecoderLayer(Layer):
         a = ops.linear(ops.rope_attention(ops.linear(y, self.qkv_proj), cos, sin, self.nh, self.nkv, causal=True),
                        self.o_proj)
         y2, h2 = ops.rms_norm(a, self.post_attention_layernorm, eps, residual=h)
+        return self._ffn(y2), h2
+
+    def _ffn(self, y2):
         if self.is_moe:
             m = self.moe(y2)
             if self.shared is not None:
                 m = m + self.shared(y2)
+            return m
+        return self.mlp(y2)
+
+    @staticmethod
+    def _skinny_mlp(expert, y2):
+        return ops.skinny_linear(ops.swiglu(ops.skinny_linear(y2, expert.gate_up)), expert.down)
+
+    def _decode_ffn(self, y2):
+        """The FFN of a decode step.  Up to ``ops.moe_decode.ROUTED_ROWS`` rows: the selected
+        experts streamed once (``ops.moe_decode_ffn``), dense and shared MLPs on the skinny GEMMs;
+        nothing is read from the device.  More rows (a decode step of a larger batch), and fp8
+        experts, which the kernels do not cover, take ``MoELayer.forward``; the skinny ops fall
+        back to ``ops.linear`` by themselves (such a step is for the launch loop, not for
+        ``graph=True``)."""
+        if not self.is_moe:
+            return self._skinny_mlp(self.mlp, y2)
+        moe = self.moe
+        if self.cfg.use_fp8_experts or y2.numel() // y2.shape[-1] > ops.moe_decode.ROUTED_ROWS:
+            m = moe(y2)
         else:
-            m = self.mlp(y2)
-        return m, h2
+            gate_up, down = moe.stacked_experts()
+            m = ops.moe_decode_ffn(y2, moe.gate.weight, gate_up, down, moe.top_k,
+                                   renorm=moe.gate.gate_type != "naive" and moe.top_k > 1)
+        if self.shared is not None:
+            m = ops.add(m, self._skinny_mlp(self.shared, y2))
+        return m
+
+    def forward_cached(self, x, residual, cos, sin, cache, layer_idx, prefill, extend=False):
+        """``forward`` for inference with a KV cache, as ``LlamaDecoderLayer.forward_cached``:
+        prefill and extends of more than ``ops.skinny.MAX_ROWS`` rows run the training kernels
+        and ``MoELayer.forward`` (its balance loss is ignored); a decode step and shorter
+        extends run the weight-streaming kernels and ``ops.moe_decode_ffn``."""
+        eps = self.cfg.rms_norm_eps
+        if residual is None:
+            h = x
+            y = ops.rms_norm(x, self.input_layernorm, eps)
+        else:
+            y, h = ops.rms_norm(x, self.input_layernorm, eps, residual=residual)
+        if prefill:
+            packed, a = prefill_qkv_attention(y, self.qkv_proj, None, cos, sin, self.nh, self.nkv)
+            ops.kv_append(packed, cache, layer_idx, self.nh, self.nkv)
+        elif extend and x.shape[0] * x.shape[1] > ops.skinny.MAX_ROWS:
+            q = ops.kv_append(ops.linear(y, self.qkv_proj), cache, layer_idx, self.nh, self.nkv, cos, sin)
+            a = ops.extend_attention(q, cache, layer_idx).view(x.shape[0], x.shape[1], -1)
+        else:
+            q = ops.kv_append(ops.skinny_linear(y, self.qkv_proj), cache, layer_idx, self.nh, self.nkv, cos, sin)
+            if extend:
+                a = ops.extend_attention(q, cache, layer_idx).view(x.shape[0], x.shape[1], -1)
+            else:
+                a = ops.decode_attention(q, cache, layer_idx).view(x.shape[0], 1, -1)
+            a = ops.skinny_linear(a, self.o_proj)
+            y2, h2 = ops.rms_norm(a, self.post_attention_layernorm, eps, residual=h)
+            return self._decode_ffn(y2), h2
+        a = ops.linear(a, self.o_proj)
+        y2, h2 = ops.rms_norm(a, self.post_attention_layernorm, eps, residual=h)
+        return self._ffn(y2), h2
 
 
-class ErnieMoEForCausalLM(Layer):
+class ErnieMoEForCausalLM(Layer, GenerationMixin):
+    """Generation (models/generation.py): every ``generate`` option of the dense models.  The
+    decode kernels ``ops.decode_attention`` / ``ops.extend_attention`` take 1, 2, 4 or 8 query
+    heads per KV head; the 20 / 4 heads of the ernie-moe-21b-a3b preset (5 per KV head) are
+    refused by them and run the plain-torch attention, which reads the lengths from the
+    device -- ``graph=True`` needs a head ratio the kernels take."""
+
     def __init__(self, cfg: ErnieMoEConfig, device=None, ep_group=None):
         super().__init__("ernie_moe")
         self.cfg = cfg
@@ -223,3 +286,36 @@ class ErnieMoEForCausalLM(Layer):
         if aux and self.cfg.aux_loss_coeff:
             loss = ops.add(loss, ops.scale(ops.stack_mean(aux), self.cfg.aux_loss_coeff))
         return loss
+
+    # ---- generation hooks (models/generation.py)
+    def _check_generation_supported(self):
+        super()._check_generation_supported()
+        for layer in self.layers:
+            if layer.is_moe and layer.moe.ep > 1:
+                raise NotImplementedError("generate() with expert parallelism is not implemented")
+        if self.cfg.capacity_factor is not None:
+            # the padding of a right-padded prompt would compete with real tokens for capacity
+            raise NotImplementedError("generate() with a capacity factor is not implemented")
+
+    def _cached_hidden(self, input_ids, cache, prefill, extend=False):
+        x = ops.embedding(input_ids, self.embed_tokens)
+        residual = None
+        for i, layer in enumerate(self.layers):
+            x, residual = layer.forward_cached(x, residual, self.rope_cos, self.rope_sin, cache, i, prefill, extend)
+        y, _ = ops.rms_norm(x, self.norm, self.cfg.rms_norm_eps, residual=residual)
+        return y
+
+    def _prefill_hidden(self, input_ids, cache):
+        return self._cached_hidden(input_ids, cache, True)
+
+    def _extend_hidden(self, input_ids, cache):
+        return self._cached_hidden(input_ids, cache, False, True)
+
+    def _decode_hidden(self, tokens, cache):
+        return self._cached_hidden(tokens, cache, False)
+
+    def _max_positions(self):
+        return self.rope_cos.shape[0]
+
+    def _lm_logits(self, y):
+        return ops.skinny_linear(y, self.lm_head)

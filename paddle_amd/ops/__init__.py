@@ -16,3 +16,5 @@ from . import sampling  # noqa: F401
 from .sampling import SamplerState, philox_uniform, sample_step, sample_tokens  # noqa: F401
 from . import speculative  # noqa: F401
 from .speculative import SpecState, spec_commit, spec_judge, spec_kernel_ok, spec_margins, spec_verify  # noqa: F401
+from . import moe_decode  # noqa: F401
+from .moe_decode import moe_decode_ok, moe_decode_route, moe_decode_ffn, moe_decode_default_splits  # noqa: F401

@@ -97,6 +97,12 @@ _SIGS = {
     "pa_gemm_skinny_f8_splits": [_I, _I],
     "pa_gemm_skinny_f8_ws_floats": [_I, _I, _I],
     "pa_gemm_skinny_f8": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _L, _L, _L, _I, _I, _P],
+    "pa_moe_decode_ok": [_I, _I, _I, _I, _I, _L, _P, _P, _P, _P],
+    "pa_moe_decode_route_ok": [_I, _I, _I, _I, _L, _P, _P],
+    "pa_moe_decode_splits": [_I, _I, _I],
+    "pa_moe_decode_ws_floats": [_I, _I, _I, _I, _I, _I],
+    "pa_moe_decode_route": [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "pa_moe_decode_ffn": [_P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P],
     "pa_fp8w_dequant": [_P, _P, _P, _L, _L, _L, _L, _P],
     "pa_sample_ok": [_I, _I, _I, _L, _P],
     "pa_philox_uniform": [ctypes.c_ulonglong, _P, _I, _P, _I, _P],

@@ -44,6 +44,7 @@ _DEFAULTS = {
     "defer_expert_wgrad": True,  # ops/grouped.py: experts' dW once per step over all micro-batches (ops/accum.py)
     "skinny_gemm": True,  # ops/skinny.py: decode-step GEMMs (M <= 16) on the weight-streaming kernel; off = ops.linear / linear_t
     "skinny_fp8": True,  # ops/skinny_fp8.py: decode-step GEMMs of an Fp8Weight on the e4m3 weight-streaming kernel; off = dequant + the bf16 path
+    "moe_decode": True,  # ops/moe_decode.py: MoE FFN of a decode step (M <= 16) on the expert-streaming kernels; off = the plain-torch definition
     "fp8_wgrad": False,  # ops/grouped.py: fp8 expert dW (measured slower, profiles/r5_moe_fp8_wgrad_NEGATIVE.md)
 }
 
