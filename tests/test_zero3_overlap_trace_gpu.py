@@ -65,7 +65,11 @@ def _worker(rank, world, port, q):
         model = LlamaForCausalLM(cfg, device="cuda")
         opt = ShardedStage3(model, lr=1e-4, grad_clip=1.0, dp_comm="direct", prefetch=True)
         assert opt._direct is not None
-        ids = torch.randint(0, cfg.vocab_size, (4, 513), generator=torch.Generator().manual_seed(rank)).cuda()
+        # 32 sequences: the traced step must be bound by the GPU, not by kernel launches.
+        # With 4 the host (tracer on) can issue kernels slower than the GPU runs them; the
+        # compute queue then idles between units, and the rank that reaches each barrier
+        # last finishes its collectives inside those gaps: nothing left to overlap.
+        ids = torch.randint(0, cfg.vocab_size, (32, 513), generator=torch.Generator().manual_seed(rank)).cuda()
 
         def step():
             with tape.recording() as t:
