@@ -236,15 +236,17 @@ __global__ __launch_bounds__(256) void momentum_multi_kernel(const MomT* __restr
   }
 }
 
-// sum of squares (for global-norm clipping): out[0] += sum(x^2); 16-B vector loads.
+// sum of squares (for global-norm clipping): out[0] += sum(x^2); 16-B vector loads over
+// the first n8 groups of 8, scalar loads for the rest (n8 == 0: x is not 16 B-aligned,
+// e.g. a gradient that is a view at an odd offset of a flat buffer).
 // Every block stores its partial and a one-block pass adds the partials in a fixed
 // order (no float atomics): the same bits every run, so the clip coefficient that
 // scales every gradient is reproducible.
 template <typename T>
-__global__ __launch_bounds__(256) void sumsq_kernel(const T* __restrict__ x, long n, float* __restrict__ part) {
+__global__ __launch_bounds__(256) void sumsq_kernel(const T* __restrict__ x, long n, long n8,
+                                                    float* __restrict__ part) {
   __shared__ float red[4];
   float s = 0.f;
-  const long n8 = n / 8;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
     float v[8];
     load8(x + i * 8, v);
@@ -354,11 +356,14 @@ PA_EXPORT int pa_sumsq_parts() { return stream_grid(1L << 40, 256); }
 PA_EXPORT int pa_sumsq(int dtype, const void* x, long n, float* out, float* part, hipStream_t st) {
   if (n == 0) return 0;
   if (part == nullptr) return (int)hipErrorInvalidValue;
-  const int grid = stream_grid((n + 7) / 8, 256);
+  // the vector loads need 16 B alignment; any other pointer takes the scalar loop alone
+  const bool aligned = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  const long n8 = aligned ? n / 8 : 0;
+  const int grid = aligned ? stream_grid((n + 7) / 8, 256) : stream_grid(n, 256);
   if (dtype == 1)
-    hipLaunchKernelGGL(sumsq_kernel<u16>, dim3(grid), dim3(256), 0, st, (const u16*)x, n, part);
+    hipLaunchKernelGGL(sumsq_kernel<u16>, dim3(grid), dim3(256), 0, st, (const u16*)x, n, n8, part);
   else
-    hipLaunchKernelGGL(sumsq_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, n, part);
+    hipLaunchKernelGGL(sumsq_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, n, n8, part);
   hipLaunchKernelGGL(sumsq_finish_kernel, dim3(1), dim3(256), 0, st, part, grid, out);
   PA_LAUNCH_CHECK();
 }

@@ -168,10 +168,14 @@ def sumsq(x, out=None):
     The kernel's second pass adds into ``out`` with a plain read-modify-write: calls
     that accumulate into one ``out`` must run on one stream (they do: the clip and
     the sharded optimizers call this on the current stream), which also fixes the
-    order of the sum."""
+    order of the sum.  ``x`` may start at any element of a larger buffer (a gradient that is
+    a view into a flat buffer): the kernel's 16-byte vector loads run only behind a 16
+    B-aligned pointer, any other pointer takes its scalar loop."""
     if out is None:
         out = torch.zeros(1, dtype=torch.float32, device=x.device)
     if x.is_cuda:
+        if not x.is_contiguous():
+            raise ValueError("sumsq: contiguous tensor required")
         # per-block partials, summed in a fixed order by the kernel's second pass
         part = torch.empty(N.lib().pa_sumsq_parts(), dtype=torch.float32, device=x.device)
         N.call("pa_sumsq", N.dt(x), N.ptr(x), x.numel(), N.ptr(out), N.ptr(part), N.stream())
