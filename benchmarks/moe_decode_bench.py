@@ -18,6 +18,11 @@ read reaches on an MI355X.  Before any timing the two outputs are compared.
 query heads per KV head, which the decode attention kernel takes) at context 512.
 
     python benchmarks/moe_decode_bench.py --step --md moe_decode_bench_table.md
+
+``--fp8`` measures the e4m3 kernels (csrc/kernels/moe_decode_f8.hip) instead, with the same
+method: against the bf16 kernels on ``dequant()`` of the same codes, against dequantising the
+selected experts first, and over forced (gate|up, down) K-slice counts; with ``--step``
+the decode step before and after ``quantize_weights()`` (profiles/moe_decode_fp8_bench.md).
 """
 from __future__ import annotations
 
@@ -47,13 +52,15 @@ class Variant:
     """One graph: a pass over the rotating layers (timed as a launch loop, and reported so, if
     the pass cannot be captured)."""
 
-    def __init__(self, name, fns):
+    def __init__(self, name, fns, capture=True):
         self.name, self.n, self.fns = name, len(fns), fns
         for f in fns:
             f()
         torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
+        self.graph = torch.cuda.CUDAGraph() if capture else None
         try:
+            if not capture:
+                raise RuntimeError("timed as a launch loop")
             with torch.cuda.graph(self.graph):
                 for f in fns:
                     f()
@@ -131,13 +138,80 @@ def bench_rows(layers, M, repeats, window_ms, dev="cuda"):
                 timing="graph replay" if base.graph is not None and ours.graph is not None else "launch loop")
 
 
+# ---------------------------------------------------------------------- --fp8
+# (gate|up, down) K-slice candidates of moe_decode_f8.hip; None = pa_moe_decode_f8_splits' rule
+SPLITS = [None, (1, 1), (2, 2), (4, 4), (8, 4), (8, 6)]
+
+
 @torch.no_grad()
-def bench_step(B, prompt=512, steps=32, rounds=3, dev="cuda"):
+def bench_rows_fp8(layers, q_layers, M, repeats, window_ms, dev="cuda"):
+    """The e4m3 kernels against (a) the bf16 kernels on the same experts and (b) what a quantised
+    model would do without them: dequantise the selected experts, then the bf16 kernels.  The
+    selection of (b) is read from the routing before any timing (a static index tensor, the
+    router restricted to those columns picks the same experts), so (b) is captured too."""
+    g = torch.Generator(device=dev).manual_seed(M)
+    xs = [torch.randn(M, H, device=dev, generator=g).to(torch.bfloat16) for _ in layers]
+    kernel = ops.moe_decode.moe_decode_kernel
+    a_fns, b_fns, distinct, err = [], [], 0, 0.0
+    for x, moe, (gu8, dn8) in zip(xs, layers, q_layers):
+        gw = moe.gate.weight
+        idx, _ = ops.moe_decode_route(x, gw, K)
+        sel = torch.unique(idx.reshape(-1).long())
+        distinct += sel.numel()
+        gw_sel = gw[:, sel].contiguous()
+        gu, dn = gu8.dequant(), dn8.dequant()  # (a) runs on exactly the numbers the codes hold
+        y8, ya = kernel(x, gw, gu8, dn8, K), kernel(x, gw, gu, dn, K)
+        yb = kernel(x, gw_sel, gu8.dequant(experts=sel), dn8.dequant(experts=sel), K)
+        err = max(err, float((y8.float() - ya.float()).abs().max()), float((yb.float() - ya.float()).abs().max()))
+        a_fns.append(lambda x=x, gw=gw, gu=gu, dn=dn: kernel(x, gw, gu, dn, K))
+        b_fns.append(lambda x=x, gw=gw_sel, gu8=gu8, dn8=dn8, sel=sel: kernel(
+            x, gw, gu8.dequant(experts=sel), dn8.dequant(experts=sel), K))
+    # (b) is not captured (a capture of its pass, which allocates the images, failed when it was
+    # tried; the cause was not looked for): a launch loop, so its numbers include the launch cost
+    # of its 6 launches (2 more than the kernels' 4)
+    variants = [Variant("bf16 kernels", a_fns), Variant("dequant(selected) + bf16 kernels", b_fns, capture=False)]
+    rule = list(ops.moe_decode_fp8_default_splits(H, I))
+    for splits in SPLITS:
+        variants.append(Variant(f"fp8 splits {list(splits) if splits else rule}" + ("" if splits else " (rule)"),
+                                [lambda x=x, moe=moe, p=p, s=splits: kernel(x, moe.gate.weight, *p, K, num_splits=s)
+                                 for x, moe, p in zip(xs, layers, q_layers)]))
+    for v in variants:
+        v.calibrate(window_ms)
+    for _ in range(repeats):
+        for v in variants:
+            v.measure()
+    a = statistics.median(variants[0].us)
+    spread = (max(variants[0].us) - min(variants[0].us)) / a
+    sel8 = distinct / len(layers) * EXPERT_BYTES / 2
+    out = dict(M=M, layers=len(layers), repeats=repeats, distinct_experts_per_layer=round(distinct / len(layers), 2),
+               selected_fp8_MB=round(sel8 / 1e6, 1), bf16_us=round(a, 2), bf16_spread_pct=round(100 * spread, 2),
+               max_abs_diff_to_bf16=round(err, 5), variants=[])
+    for v in variants[1:]:
+        us = statistics.median(v.us)
+        out["variants"].append(dict(name=v.name, us=round(us, 2), spread_pct=round(100 * (max(v.us) - min(v.us)) / us, 2),
+                                    ratio_to_bf16=round(us / a, 4), faster_than_bf16_by_more_than_its_spread=bool(
+                                        us < a * (1 - spread)),
+                                    selected_TB_per_s=round(sel8 / (us * 1e-6) / 1e12, 3),
+                                    fraction_of_streaming=round(sel8 / (us * 1e-6) / 1e12 / STREAM_TBS, 3),
+                                    graph=v.graph is not None))
+    return out
+
+
+def model_bytes(model):
+    return sum(t.numel() * t.element_size() for t in list(model.parameters()) + list(model.buffers()))
+
+
+@torch.no_grad()
+def bench_step(B, prompt=512, steps=32, rounds=3, dev="cuda", quantize=False):
     """One decode step of ernie-moe-a3b-8l with 20 / 5 heads and grouped experts: the launch loop
-    and the replayed graph."""
+    and the replayed graph.  ``quantize``: after ``quantize_weights()``."""
     torch.manual_seed(0)
     cfg = ErnieMoEConfig(**ERNIE_MOE_CONFIGS["ernie-moe-a3b-8l"], num_key_value_heads=5, grouped_experts=True)
     model = ErnieMoEForCausalLM(cfg, device=dev).eval()
+    nbytes = model_bytes(model)
+    if quantize:
+        model.quantize_weights()
+        nbytes = model_bytes(model)
     ids = torch.randint(1, cfg.vocab_size, (B, prompt), device=dev)
     total = (2 * rounds + 2) * steps + 8
     cache = model.init_cache(B, prompt + total)
@@ -167,8 +241,8 @@ def bench_step(B, prompt=512, steps=32, rounds=3, dev="cuda"):
         torch.cuda.synchronize()
         replay.append(t0.elapsed_time(t1) / steps)
     lo, rp = statistics.median(loop), statistics.median(replay)
-    return dict(model="ernie-moe-a3b-8l, 20/5 heads, grouped experts", B=B, context=prompt,
-                launch_loop_step_ms=round(lo, 3), launch_loop_spread_pct=round(100 * (max(loop) - min(loop)) / lo, 2),
+    return dict(model="ernie-moe-a3b-8l, 20/5 heads, grouped experts" + (", quantize_weights()" if quantize else ""),
+                B=B, context=prompt, model_GB=round(nbytes / 1e9, 3), launch_loop_step_ms=round(lo, 3), launch_loop_spread_pct=round(100 * (max(loop) - min(loop)) / lo, 2),
                 graph_step_ms=round(rp, 3), graph_spread_pct=round(100 * (max(replay) - min(replay)) / rp, 2))
 
 
@@ -196,6 +270,8 @@ def main():
     ap.add_argument("--window-ms", type=float, default=100.0, help="least length of one timed window")
     ap.add_argument("--layers", type=int, default=4, help="rotating MoE layers (1.5 GB of experts each)")
     ap.add_argument("--step", action="store_true", help="also time an ernie-moe-a3b-8l decode step at B = 1 and 8")
+    ap.add_argument("--fp8", action="store_true", help="the e4m3 kernels (moe_decode_f8.hip) against the bf16 kernels on "
+                    "the same experts and against dequantising the selected experts first; JSON lines only")
     ap.add_argument("--md", default=None, help="write the results as markdown tables to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -204,18 +280,26 @@ def main():
                           routed_rows_in_tree=ops.moe_decode.ROUTED_ROWS)), flush=True)
     layers = make_layers(args.layers, "cuda")
     rows, steps = [], []
-    for M in ROWS:
-        r = bench_rows(layers, M, args.repeats, args.window_ms)
-        rows.append(r)
-        print(json.dumps(r), flush=True)
+    if args.fp8:
+        with torch.no_grad():
+            q_layers = [tuple(ops.quantize_experts_fp8(t) for t in moe.stacked_experts()) for moe in layers]
+        for M in ROWS:
+            print(json.dumps(bench_rows_fp8(layers, q_layers, M, args.repeats, args.window_ms)), flush=True)
+        del q_layers
+    else:
+        for M in ROWS:
+            r = bench_rows(layers, M, args.repeats, args.window_ms)
+            rows.append(r)
+            print(json.dumps(r), flush=True)
     del layers
     torch.cuda.empty_cache()
     if args.step:
         for B in (1, 8):
-            r = bench_step(B)
-            steps.append(r)
-            print(json.dumps(r), flush=True)
-    if args.md:
+            for quantize in ((False, True) if args.fp8 else (False,)):
+                r = bench_step(B, quantize=quantize)
+                steps.append(r)
+                print(json.dumps(r), flush=True)
+    if args.md and not args.fp8:
         write_md(args.md, rows, steps)
 
 

@@ -23,7 +23,7 @@ from ..nn import Layer
 from ..ops import grouped as _grouped
 from ..ops.fp8 import fp8_linear
 from ..ops.fused import param_ready
-from .generation import GenerationMixin, prefill_qkv_attention
+from .generation import GenerationMixin, dense_weight, prefill_qkv_attention
 from .llama import _dt, _param
 
 
@@ -79,7 +79,7 @@ class SwiGLUExpert(Layer):
 
     def forward(self, x):
         lin = fp8_linear if self.fp8 else ops.linear
-        return lin(ops.swiglu(lin(x, self.gate_up)), self.down)
+        return lin(ops.swiglu(lin(x, dense_weight(self.gate_up, x))), dense_weight(self.down, x))
 
 
 class GroupedSwiGLUExperts(Layer):
@@ -114,12 +114,17 @@ class GroupedSwiGLUExperts(Layer):
         path; or host ints)."""
         if x.shape[0] == 0:
             return x
-        param_ready(self.gate_up)
-        param_ready(self.down)
-        if self.fp8 and _grouped.supported_f8(x, self.gate_up, self.down):
-            return _grouped.grouped_swiglu_mlp(x, self.gate_up, self.down, counts, fp8=True)
-        if _grouped.supported(x, self.gate_up, self.down):
-            return _grouped.grouped_swiglu_mlp(x, self.gate_up, self.down, counts)
+        gate_up, down = self.gate_up, self.down
+        if isinstance(gate_up, ops.Fp8ExpertWeights):
+            # quantize_weights(): transient images of this layer's two stacks, gone on return
+            gate_up, down = dense_weight(gate_up, x), dense_weight(down, x)
+        else:
+            param_ready(gate_up)
+            param_ready(down)
+        if self.fp8 and _grouped.supported_f8(x, gate_up, down):
+            return _grouped.grouped_swiglu_mlp(x, gate_up, down, counts, fp8=True)
+        if _grouped.supported(x, gate_up, down):
+            return _grouped.grouped_swiglu_mlp(x, gate_up, down, counts)
         if torch.is_tensor(counts):
             counts = counts.tolist()
         n, N = self.num_experts, x.shape[0]
@@ -129,8 +134,8 @@ class GroupedSwiGLUExperts(Layer):
         starts = torch.cumsum(ct, 0) - ct
         dest = e_of_row * C + (torch.arange(N, device=x.device) - starts[e_of_row])
         xp = x.new_zeros(n * C, x.shape[1]).index_copy(0, dest, x).view(n, C, -1)
-        h = ops.swiglu(torch.bmm(xp, self.gate_up.to(x.dtype)))
-        return torch.bmm(h, self.down.to(x.dtype)).view(n * C, -1).index_select(0, dest)
+        h = ops.swiglu(torch.bmm(xp, gate_up.to(x.dtype)))
+        return torch.bmm(h, down.to(x.dtype)).view(n * C, -1).index_select(0, dest)
 
 
 class ErnieMoEDecoderLayer(Layer):
@@ -180,8 +185,8 @@ class ErnieMoEDecoderLayer(Layer):
             y = ops.rms_norm(x, self.input_layernorm, eps)
         else:
             y, h = ops.rms_norm(x, self.input_layernorm, eps, residual=residual)
-        a = ops.linear(ops.rope_attention(ops.linear(y, self.qkv_proj), cos, sin, self.nh, self.nkv, causal=True),
-                       self.o_proj)
+        a = ops.rope_attention(ops.linear(y, dense_weight(self.qkv_proj, y)), cos, sin, self.nh, self.nkv, causal=True)
+        a = ops.linear(a, dense_weight(self.o_proj, a))
         y2, h2 = ops.rms_norm(a, self.post_attention_layernorm, eps, residual=h)
         return self._ffn(y2), h2
 
@@ -199,9 +204,10 @@ class ErnieMoEDecoderLayer(Layer):
 
     def _decode_ffn(self, y2):
         """The FFN of a decode step.  Up to ``ops.moe_decode.ROUTED_ROWS`` rows: the selected
-        experts streamed once (``ops.moe_decode_ffn``), dense and shared MLPs on the skinny GEMMs;
-        nothing is read from the device.  More rows (a decode step of a larger batch), and fp8
-        experts, which the kernels do not cover, take ``MoELayer.forward``; the skinny ops fall
+        experts streamed once (``ops.moe_decode_ffn``; after ``quantize_weights()`` their e4m3
+        codes), dense and shared MLPs on the skinny GEMMs; nothing is read from the device.  More
+        rows (a decode step of a larger batch), and ``use_fp8_experts`` (fp8 activations), which
+        the kernels do not cover, take ``MoELayer.forward``; the skinny ops fall
         back to ``ops.linear`` by themselves (such a step is for the launch loop, not for
         ``graph=True``)."""
         if not self.is_moe:
@@ -229,10 +235,10 @@ class ErnieMoEDecoderLayer(Layer):
         else:
             y, h = ops.rms_norm(x, self.input_layernorm, eps, residual=residual)
         if prefill:
-            packed, a = prefill_qkv_attention(y, self.qkv_proj, None, cos, sin, self.nh, self.nkv)
+            packed, a = prefill_qkv_attention(y, dense_weight(self.qkv_proj, y), None, cos, sin, self.nh, self.nkv)
             ops.kv_append(packed, cache, layer_idx, self.nh, self.nkv)
         elif extend and x.shape[0] * x.shape[1] > ops.skinny.MAX_ROWS:
-            q = ops.kv_append(ops.linear(y, self.qkv_proj), cache, layer_idx, self.nh, self.nkv, cos, sin)
+            q = ops.kv_append(ops.linear(y, dense_weight(self.qkv_proj, y)), cache, layer_idx, self.nh, self.nkv, cos, sin)
             a = ops.extend_attention(q, cache, layer_idx).view(x.shape[0], x.shape[1], -1)
         else:
             q = ops.kv_append(ops.skinny_linear(y, self.qkv_proj), cache, layer_idx, self.nh, self.nkv, cos, sin)
@@ -243,7 +249,7 @@ class ErnieMoEDecoderLayer(Layer):
             a = ops.skinny_linear(a, self.o_proj)
             y2, h2 = ops.rms_norm(a, self.post_attention_layernorm, eps, residual=h)
             return self._decode_ffn(y2), h2
-        a = ops.linear(a, self.o_proj)
+        a = ops.linear(a, dense_weight(self.o_proj, a))
         y2, h2 = ops.rms_norm(a, self.post_attention_layernorm, eps, residual=h)
         return self._ffn(y2), h2
 
@@ -278,7 +284,7 @@ class ErnieMoEForCausalLM(Layer, GenerationMixin):
             if layer.is_moe and layer.moe.l_aux is not None:
                 aux.append(layer.moe.l_aux)
         y, _ = ops.rms_norm(x, self.norm, self.cfg.rms_norm_eps, residual=residual)
-        logits = ops.linear(y, self.lm_head)
+        logits = ops.linear(y, dense_weight(self.lm_head, y))
         if labels is None:
             return logits
         loss = ops.softmax_cross_entropy(logits, labels, inplace_grad=True)
@@ -288,6 +294,29 @@ class ErnieMoEForCausalLM(Layer, GenerationMixin):
         return loss
 
     # ---- generation hooks (models/generation.py)
+    def _quant_targets(self):
+        """Attention matrices, the dense and shared MLPs (``Fp8Weight``s on the skinny GEMMs) and
+        the grouped expert stacks (``Fp8ExpertWeights`` on ``ops.moe_decode_ffn``).  The router,
+        embeddings and norms stay.  Prefill, long extends and decode steps of more than 16 rows
+        run on transient dequantised images, for one MoE layer's two stacks at a time."""
+        if self.cfg.use_fp8_experts:
+            raise NotImplementedError("quantize_weights() with use_fp8_experts=True is not implemented")
+        targets = []
+        for layer in self.layers:
+            targets += [(layer, "qkv_proj"), (layer, "o_proj")]
+            if not layer.is_moe:
+                targets += [(layer.mlp, "gate_up"), (layer.mlp, "down")]
+                continue
+            if layer.moe.ep > 1:
+                raise NotImplementedError("quantize_weights() with expert parallelism is not implemented")
+            if not layer.moe.grouped:
+                raise NotImplementedError("quantize_weights() needs stacked expert weights: build the model with "
+                                          "grouped_experts=True")
+            targets += [(layer.moe.experts, "gate_up"), (layer.moe.experts, "down")]
+            if layer.shared is not None:
+                targets += [(layer.shared, "gate_up"), (layer.shared, "down")]
+        return targets
+
     def _check_generation_supported(self):
         super()._check_generation_supported()
         for layer in self.layers:

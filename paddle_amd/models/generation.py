@@ -126,7 +126,7 @@ def dense_weight(w, x):
     """A layer weight as the dense tensor the training / prefill kernels take: ``w`` itself,
     or for an ``ops.Fp8Weight`` a transient dequantised image in ``x``'s dtype (exact: see
     ops/skinny_fp8.py), which is inference only."""
-    if not isinstance(w, ops.Fp8Weight):
+    if not isinstance(w, (ops.Fp8Weight, ops.Fp8ExpertWeights)):  # the latter: a whole expert stack
         return w
     if torch.is_grad_enabled() or _tape.current() is not None:
         raise RuntimeError("a model with quantised weights is inference only: run it under torch.no_grad() "
@@ -254,23 +254,31 @@ class GenerationMixin:
             raise RuntimeError(f"quantize_weights: the weights are already quantised ({self._pa_quantized})")
         if getattr(self, "tp", None) is not None:
             raise NotImplementedError("quantize_weights() with tensor parallelism is not implemented")
-        if not self._quant_weights:
-            raise NotImplementedError(f"quantize_weights() is not implemented for {type(self).__name__}")
+        targets = self._quant_targets()
         if include_head and getattr(self, "lm_head", None) is None:
             raise ValueError("quantize_weights: include_head=True needs an untied lm_head")
-        targets = [(layer, n) for layer in self.layers for n in self._quant_weights]
         if include_head:
             targets.append((self, "lm_head"))
         for mod, n in targets:  # before anything is changed
             if not torch.isfinite(getattr(mod, n)).all():
                 raise ValueError(f"quantize_weights: {n} has a non-finite value")
         for mod, n in targets:
-            w8 = ops.quantize_weight_fp8(getattr(mod, n).detach())
+            w = getattr(mod, n).detach()
+            # a 3-D parameter is a stack of experts: one scale per (expert, column)
+            w8 = ops.quantize_experts_fp8(w) if w.dim() == 3 else ops.quantize_weight_fp8(w)
             delattr(mod, n)  # the parameter (and whatever ops cached on it) goes
             setattr(mod, n, w8)
         self._pa_quantized = fmt
         self.state_dict = self.load_state_dict = self.set_state_dict = _quantized_state_error
         return self.eval()
+
+    def _quant_targets(self):
+        """The (module, attribute name) pairs ``quantize_weights()`` converts, or
+        ``NotImplementedError``: by default ``_quant_weights`` of every decoder layer.  A model
+        with nested matrices (expert stacks, shared experts) lists them itself."""
+        if not self._quant_weights:
+            raise NotImplementedError(f"quantize_weights() is not implemented for {type(self).__name__}")
+        return [(layer, n) for layer in self.layers for n in self._quant_weights]
 
     def _check_generation_supported(self):
         if getattr(self, "tp", None) is not None:

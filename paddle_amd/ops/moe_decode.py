@@ -22,6 +22,16 @@ On the GPU a call is four launches (route, gate|up, down, combine) whose grids c
 M, k, E, H, I alone; nothing is read back from the device, so a call can be captured into a
 HIP graph.  ``gate_up`` keeps the model's ``[gate | up]`` column layout; no second image of the
 weights is made.
+
+**FP8 experts** (``csrc/kernels/moe_decode_f8.hip``).  ``quantize_experts_fp8(w)`` turns a stack
+``[E, K, N]`` into an :class:`Fp8ExpertWeights`: e4m3 codes ``q [E, K, N]`` and one power-of-two
+fp32 scale per (expert, output column) ``scale [E, N]`` -- ``quantize_weight_fp8``'s contract
+(ops/skinny_fp8.py) applied per expert, bit for bit.  ``q * scale`` is exact in bf16, so a
+quantised MoE FFN *is* the bf16 MoE FFN whose stacks are ``w8.dequant()``.  ``moe_decode_ffn``
+takes a pair of them for ``gate_up`` and ``down`` (both or neither); routing is unchanged.  Its
+plain-torch definition is the one above on the dequantised stacks of the selected experts only;
+on the GPU the e4m3 kernels stream the selected experts' codes once and apply the scales to the
+summed accumulators (``FLAGS_moe_decode_fp8=0`` switches these kernels off on their own).
 """
 from __future__ import annotations
 
@@ -31,8 +41,10 @@ from ..utils import flags as _flags
 from . import _native as N
 from . import fused as F
 from .skinny import MAX_ROWS
+from .skinny_fp8 import quantize_weight_fp8
 
-__all__ = ["moe_decode_ok", "moe_decode_route", "moe_decode_ffn", "moe_decode_default_splits"]
+__all__ = ["moe_decode_ok", "moe_decode_route", "moe_decode_ffn", "moe_decode_default_splits",
+           "Fp8ExpertWeights", "quantize_experts_fp8", "moe_decode_fp8_default_splits"]
 
 MAX_EXPERTS = 256
 MAX_TOP_K = 16
@@ -46,6 +58,94 @@ def moe_decode_default_splits(H, I):
     (``pa_moe_decode_splits``; no GPU needed)."""
     L = N.lib()
     return int(L.pa_moe_decode_splits(0, int(H), int(I))), int(L.pa_moe_decode_splits(1, int(H), int(I)))
+
+
+def moe_decode_fp8_default_splits(H, I):
+    """(gate|up, down) K slices of the e4m3 kernels: functions of H and I only
+    (``pa_moe_decode_f8_splits``; no GPU needed)."""
+    L = N.lib()
+    return int(L.pa_moe_decode_f8_splits(0, int(H), int(I))), int(L.pa_moe_decode_f8_splits(1, int(H), int(I)))
+
+
+# ------------------------------------------------------------------ fp8 expert stacks
+_FP8 = torch.float8_e4m3fn
+
+
+class Fp8ExpertWeights(torch.nn.Module):
+    """An expert stack ``[E, K, N]`` held as e4m3 codes ``q [E, K, N]`` and fp32 scales ``scale
+    [E, N]`` (non-persistent buffers, like ``Fp8Weight``)."""
+
+    def __init__(self, q, scale):
+        super().__init__()
+        if not (torch.is_tensor(q) and q.dtype == _FP8 and q.dim() == 3):
+            raise ValueError("Fp8ExpertWeights: q must be a 3-D torch.float8_e4m3fn tensor")
+        if not (torch.is_tensor(scale) and scale.dtype == torch.float32
+                and tuple(scale.shape) == (q.shape[0], q.shape[2])):
+            raise ValueError("Fp8ExpertWeights: scale must be fp32 of shape [E, N]")
+        self.register_buffer("q", q, persistent=False)
+        self.register_buffer("scale", scale, persistent=False)
+
+    @property
+    def shape(self):
+        return self.q.shape
+
+    @property
+    def device(self):
+        return self.q.device
+
+    @property
+    def nbytes(self):
+        return self.q.numel() + 4 * self.scale.numel()
+
+    @torch.no_grad()
+    def dequant(self, dtype=torch.bfloat16, experts=None):
+        """A fresh ``[E, K, N]`` tensor ``q * scale`` -- or ``[len(experts), K, N]`` for an index
+        tensor, which stays on its device -- in ``dtype`` (bf16 and fp32 hold the product
+        exactly for the quantiser's scales).  On the GPU in bf16: one launch of
+        ``pa_fp8w_dequant_experts``.  Indices given on the CPU are checked (``IndexError`` outside
+        ``[0, E)``); an index tensor on the GPU is not read back, so that the call stays
+        capturable: there the kernel reads nothing for an index outside ``[0, E)`` and leaves
+        that expert's rows of the result unwritten."""
+        q, s = self.q, self.scale
+        E, K, Nn = q.shape
+        sel = None if experts is None else torch.as_tensor(experts).reshape(-1).long()
+        if sel is not None and not sel.is_cuda and sel.numel() and not (0 <= int(sel.min()) and int(sel.max()) < E):
+            raise IndexError(f"Fp8ExpertWeights.dequant: expert index outside [0, {E})")
+        n = E if sel is None else sel.numel()
+        if dtype == torch.bfloat16 and q.is_cuda and Nn % 16 == 0 and q.is_contiguous() and s.is_contiguous() \
+                and q.data_ptr() % 16 == 0 and s.data_ptr() % 16 == 0 and K > 0 and 0 < n < 65536:
+            out = torch.empty(n, K, Nn, dtype=torch.bfloat16, device=q.device)
+            if sel is not None:
+                sel = sel.to(q.device).contiguous()
+            N.call("pa_fp8w_dequant_experts", N.ptr(q), N.ptr(s), N.ptr(sel), N.ptr(out), n, E, K, Nn, N.stream())
+            return out
+        if sel is not None:
+            q, s = q[sel], s[sel]
+        return (q.float() * s[:, None, :]).to(dtype)
+
+    def extra_repr(self):
+        E, K, Nn = self.q.shape
+        return f"E={E}, K={K}, N={Nn}, e4m3 codes + fp32 (expert, column) scales"
+
+
+@torch.no_grad()
+def quantize_experts_fp8(w) -> Fp8ExpertWeights:
+    """``w [E, K, N]`` (any float dtype) -> :class:`Fp8ExpertWeights`; expert ``e`` of the result
+    is ``quantize_weight_fp8(w[e])`` bit for bit.  Raises ``ValueError`` for a non-finite weight."""
+    if not (torch.is_tensor(w) and w.dim() == 3 and w.is_floating_point()):
+        raise ValueError("quantize_experts_fp8: a 3-D floating-point stack [E, K, N] is expected")
+    if not torch.isfinite(w).all():
+        raise ValueError("quantize_experts_fp8: the weight has a non-finite value")
+    q = torch.empty(w.shape, dtype=_FP8, device=w.device)
+    scale = torch.empty(w.shape[0], w.shape[2], dtype=torch.float32, device=w.device)
+    for e in range(w.shape[0]):  # one expert at a time: no fp32 image of the whole stack
+        w8 = quantize_weight_fp8(w[e])
+        q[e], scale[e] = w8.q, w8.scale
+    return Fp8ExpertWeights(q, scale)
+
+
+def _is_fp8(t):
+    return isinstance(t, Fp8ExpertWeights)
 
 
 # ------------------------------------------------------------------ the definition (plain torch)
@@ -63,7 +163,9 @@ def _shapes(x, gate_w, gate_up, down, top_k):
         raise ValueError(f"moe_decode: top_k {k} outside [1, min(E = {E}, {MAX_TOP_K})]")
     I = None
     if gate_up is not None:
-        if gate_up.dim() != 3 or down.dim() != 3 or gate_up.shape[0] != E or gate_up.shape[1] != H \
+        if _is_fp8(gate_up) != _is_fp8(down):
+            raise ValueError("moe_decode: gate_up and down must both be Fp8ExpertWeights, or neither")
+        if len(gate_up.shape) != 3 or len(down.shape) != 3 or gate_up.shape[0] != E or gate_up.shape[1] != H \
                 or gate_up.shape[2] % 2 or tuple(down.shape) != (E, gate_up.shape[2] // 2, H):
             raise ValueError(f"moe_decode: gate_up {tuple(gate_up.shape)} / down {tuple(down.shape)} do not match "
                              f"E = {E}, H = {H}")
@@ -85,15 +187,20 @@ def _route_ref(x2, gate_w, k, renorm):
     return idx.to(torch.int32), w
 
 
+def _pick(stack, e):
+    """The stack's experts ``e`` in fp32: for an fp8 stack, dequantised images of those alone."""
+    return stack.dequant(torch.float32, experts=e) if _is_fp8(stack) else stack[e].float()
+
+
 def _ffn_ref(x2, gate_up, down, idx, w):
     M, k = idx.shape
     I = down.shape[1]
     ys = []
     for t in range(M):  # row by row: a row's result cannot depend on the other rows
         e = idx[t].long()
-        gu = torch.einsum("h,khn->kn", x2[t].float(), gate_up[e].float())
+        gu = torch.einsum("h,khn->kn", x2[t].float(), _pick(gate_up, e))
         a = (torch.nn.functional.silu(gu[:, :I]) * gu[:, I:]).to(x2.dtype)
-        o = torch.einsum("ki,kih->kh", a.float(), down[e].float())
+        o = torch.einsum("ki,kih->kh", a.float(), _pick(down, e))
         acc = w[t, 0] * o[0]
         for j in range(1, k):
             acc = acc + w[t, j] * o[j]
@@ -141,6 +248,17 @@ def _problem(x, gate_w, gate_up, down, top_k, policy=True):
     x2 = _rows(x, gate_w, policy)
     if x2 is None:
         return None
+    if _is_fp8(gate_up):
+        if policy and not _flags.get("moe_decode_fp8"):
+            return None
+        ts = (gate_up.q, gate_up.scale, down.q, down.scale)
+        if not all(t.is_cuda and t.is_contiguous() for t in ts):
+            return None
+        M, H = x2.shape
+        if not N.lib().pa_moe_decode_f8_ok(M, H, gate_up.shape[2] // 2, gate_w.shape[1], int(top_k), _ld(x2),
+                                           x2.data_ptr(), gate_w.data_ptr(), *(t.data_ptr() for t in ts)):
+            return None
+        return x2
     if not (gate_up.is_cuda and down.is_cuda and gate_up.dtype == torch.bfloat16 and down.dtype == torch.bfloat16
             and gate_up.is_contiguous() and down.is_contiguous()):
         return None
@@ -188,9 +306,32 @@ def _launch_ffn(x2, gate_up, down, idx, w, splits, out=None):
     return y
 
 
-def _splits(num_splits, H, I):
+def _launch_ffn_fp8(x2, gate_up, down, idx, w, splits, out=None):
+    """The one place the three e4m3 FFN kernels are launched from; as ``_launch_ffn``."""
+    M, H = x2.shape
+    E, _, I2 = gate_up.shape
+    I, k = I2 // 2, idx.shape[1]
+    sg, sd = splits
+    nws = int(N.lib().pa_moe_decode_f8_ws_floats(M, H, I, k, sg, sd))
+    if nws < 0:
+        raise ValueError("moe_decode_ffn: the split counts need a workspace beyond 2^31 floats")
+    ws = torch.empty(nws, dtype=torch.float32, device=x2.device)
+    y = torch.empty(M, H, dtype=torch.bfloat16, device=x2.device) if out is None else out
+    N.call("pa_moe_decode_ffn_f8", N.ptr(x2), _ld(x2), N.ptr(gate_up.q), N.ptr(gate_up.scale), N.ptr(down.q),
+           N.ptr(down.scale), N.ptr(idx), N.ptr(w), N.ptr(ws), N.ptr(y), _ld(y), M, H, I, E, k, sg, sd, N.stream())
+    return y
+
+
+def _ffn(x2, gate_up, down, idx, w, num_splits):
+    H, I = x2.shape[1], down.shape[1]
+    if _is_fp8(gate_up):
+        return _launch_ffn_fp8(x2, gate_up, down, idx, w, _splits(num_splits, H, I, True))
+    return _launch_ffn(x2, gate_up, down, idx, w, _splits(num_splits, H, I))
+
+
+def _splits(num_splits, H, I, fp8=False):
     if num_splits is None:
-        return moe_decode_default_splits(H, I)
+        return moe_decode_fp8_default_splits(H, I) if fp8 else moe_decode_default_splits(H, I)
     if isinstance(num_splits, (tuple, list)):
         sg, sd = num_splits
         return int(sg), int(sd)
@@ -206,7 +347,7 @@ def moe_decode_kernel(x, gate_w, gate_up, down, top_k, renorm=True, num_splits=N
     if x2 is None:
         raise ValueError("moe_decode_kernel: the kernels do not cover this problem")
     idx, w = _launch_route(x2, gate_w, k, renorm)
-    return _launch_ffn(x2, gate_up, down, idx, w, _splits(num_splits, H, I)).view(x.shape)
+    return _ffn(x2, gate_up, down, idx, w, num_splits).view(x.shape)
 
 
 @torch.no_grad()
@@ -224,16 +365,17 @@ def moe_decode_route(x, gate_w, top_k, renorm=True):
 @torch.no_grad()
 def moe_decode_ffn(x, gate_w, gate_up, down, top_k, renorm=True, num_splits=None):
     """Top-k MoE FFN of a decode call: x [..., H] (at most 16 rows), gate_w [H, E] fp32, gate_up
-    [E, H, 2I] (``[gate | up]`` columns) and down [E, I, H] -> y like x.  ``num_splits``: K
-    slices of the two products (an int for both, or a pair; default
-    :func:`moe_decode_default_splits`)."""
+    [E, H, 2I] (``[gate | up]`` columns) and down [E, I, H] -- two tensors, or two
+    :class:`Fp8ExpertWeights` -- -> y like x.  ``num_splits``: K slices of the two products (an
+    int for both, or a pair; default :func:`moe_decode_default_splits`, for fp8 stacks
+    :func:`moe_decode_fp8_default_splits`)."""
     M, H, I, E, k = _shapes(x, gate_w, gate_up, down, top_k)
     x2 = _problem(x, gate_w, gate_up, down, k)
     if x2 is not None:
-        for p in (gate_w, gate_up, down):
+        for p in (gate_w,) if _is_fp8(gate_up) else (gate_w, gate_up, down):
             F.param_ready(p)
         idx, w = _launch_route(x2, gate_w, k, renorm)
-        return _launch_ffn(x2, gate_up, down, idx, w, _splits(num_splits, H, I)).view(x.shape)
+        return _ffn(x2, gate_up, down, idx, w, num_splits).view(x.shape)
     x2 = x.reshape(M, H)
     idx, w = _route_ref(x2, gate_w, k, bool(renorm))
     return _ffn_ref(x2, gate_up, down, idx, w).view(x.shape)
