@@ -294,6 +294,12 @@ class ErnieMoEForCausalLM(Layer, GenerationMixin):
         return loss
 
     # ---- generation hooks (models/generation.py)
+    def quantize_weights(self, fmt="fp8_e4m3", include_head=False):
+        if fmt == "mxfp4":  # before anything changes: the expert stacks need a kernel of their own
+            raise NotImplementedError("quantize_weights(fmt='mxfp4') is not implemented for ErnieMoEForCausalLM: "
+                                      "there is no mxfp4 expert-streaming kernel")
+        return super().quantize_weights(fmt, include_head)
+
     def _quant_targets(self):
         """Attention matrices, the dense and shared MLPs (``Fp8Weight``s on the skinny GEMMs) and
         the grouped expert stacks (``Fp8ExpertWeights`` on ``ops.moe_decode_ffn``).  The router,

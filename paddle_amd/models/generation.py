@@ -38,6 +38,8 @@ one power-of-two scale per (token, kv head): ops/kv_fp8.py.
 ``quantize_weights()`` turns the decoder layers' matrices into ``ops.Fp8Weight``s (e4m3 codes,
 power-of-two column scales): decode steps run them on the fp8 weight-streaming kernel,
 prefill on an exact dequantised image (ops/skinny_fp8.py).
+``quantize_weights(fmt="mxfp4")`` does the same with ``ops.Mxfp4Weight``s (e2m1 codes, one
+power-of-two scale per 32 input features: 4.25 bits per weight, ops/skinny_mxfp4.py).
 """
 from __future__ import annotations
 
@@ -124,9 +126,9 @@ def sample_next(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, ge
 
 def dense_weight(w, x):
     """A layer weight as the dense tensor the training / prefill kernels take: ``w`` itself,
-    or for an ``ops.Fp8Weight`` a transient dequantised image in ``x``'s dtype (exact: see
-    ops/skinny_fp8.py), which is inference only."""
-    if not isinstance(w, (ops.Fp8Weight, ops.Fp8ExpertWeights)):  # the latter: a whole expert stack
+    or for an ``ops.Fp8Weight`` / ``ops.Mxfp4Weight`` a transient dequantised image in ``x``'s
+    dtype (exact: see ops/skinny_fp8.py, ops/skinny_mxfp4.py), which is inference only."""
+    if not isinstance(w, (ops.Fp8Weight, ops.Mxfp4Weight, ops.Fp8ExpertWeights)):  # the last: a whole expert stack
         return w
     if torch.is_grad_enabled() or _tape.current() is not None:
         raise RuntimeError("a model with quantised weights is inference only: run it under torch.no_grad() "
@@ -247,9 +249,12 @@ class GenerationMixin:
         the same ops with those products on the e4m3 weight-streaming kernel; prefill and
         ``model(ids)`` run the usual kernels on a transient dequantised image of one layer
         matrix (the two MLP matrices of a fused SwiGLU block) at a time, which is exact.
+        ``fmt="mxfp4"``: ``ops.Mxfp4Weight``s instead -- e2m1 codes plus one power-of-two scale
+        per 32 input features of a column, on the MFMA weight-streaming kernel; every matrix
+        needs an input dimension that is a multiple of 32.
         The model is inference only afterwards.  Returns ``self``."""
-        if fmt != "fp8_e4m3":
-            raise ValueError(f"quantize_weights: unknown fmt {fmt!r} (supported: 'fp8_e4m3')")
+        if fmt not in ("fp8_e4m3", "mxfp4"):
+            raise ValueError(f"quantize_weights: unknown fmt {fmt!r} (supported: 'fp8_e4m3', 'mxfp4')")
         if getattr(self, "_pa_quantized", None) is not None:
             raise RuntimeError(f"quantize_weights: the weights are already quantised ({self._pa_quantized})")
         if getattr(self, "tp", None) is not None:
@@ -262,10 +267,15 @@ class GenerationMixin:
         for mod, n in targets:  # before anything is changed
             if not torch.isfinite(getattr(mod, n)).all():
                 raise ValueError(f"quantize_weights: {n} has a non-finite value")
+            if fmt == "mxfp4" and (getattr(mod, n).dim() != 2 or getattr(mod, n).shape[0] % 32):
+                raise ValueError(f"quantize_weights: fmt 'mxfp4' needs 2-D weights whose input dimension is a "
+                                 f"multiple of 32; {n} is {tuple(getattr(mod, n).shape)}")
         for mod, n in targets:
             w = getattr(mod, n).detach()
-            # a 3-D parameter is a stack of experts: one scale per (expert, column)
-            w8 = ops.quantize_experts_fp8(w) if w.dim() == 3 else ops.quantize_weight_fp8(w)
+            if fmt == "mxfp4":
+                w8 = ops.quantize_weight_mxfp4(w)
+            else:  # a 3-D parameter is a stack of experts: one scale per (expert, column)
+                w8 = ops.quantize_experts_fp8(w) if w.dim() == 3 else ops.quantize_weight_fp8(w)
             delattr(mod, n)  # the parameter (and whatever ops cached on it) goes
             setattr(mod, n, w8)
         self._pa_quantized = fmt

@@ -24,6 +24,7 @@ from ..utils import flags as _flags
 from . import _native as N
 from . import fused as F
 from . import skinny_fp8 as _F8
+from . import skinny_mxfp4 as _MX4
 
 __all__ = ["skinny_ok", "skinny_linear", "skinny_linear_t", "skinny_default_splits"]
 
@@ -143,7 +144,8 @@ def skinny_kernel(x, w, *, b_kmaj=False, bias=None, act=None, num_splits=None):
 
 @torch.no_grad()
 def skinny_linear(x, w, bias=None, act=None, num_splits=None):
-    """x [..., K] (at most 16 rows) times w [K, N] (a bf16 tensor or an ``ops.Fp8Weight``) with
+    """x [..., K] (at most 16 rows) times w [K, N] (a bf16 tensor, an ``ops.Fp8Weight`` or an
+    ``ops.Mxfp4Weight``) with
     an optional epilogue:
 
     * ``act=None``: ``x w (+ bias)`` -- ``ops.linear``;
@@ -159,6 +161,12 @@ def skinny_linear(x, w, bias=None, act=None, num_splits=None):
         if out is not None:
             return out
         w, num_splits = _F8.dequant_for(x, w), None
+    elif isinstance(w, _MX4.Mxfp4Weight):
+        # mxfp4 weight (ops/skinny_mxfp4.py): the same arrangement
+        out = _MX4.linear(x, w, bias, act, num_splits)
+        if out is not None:
+            return out
+        w, num_splits = _MX4.dequant_for(x, w), None
     prob = _problem(x, w, False, bias, act, num_splits)
     if prob is not None:
         return _run(prob, x, w, False, bias)
