@@ -55,6 +55,7 @@ from ..ops import fused as F
 from ..ops import gemm as _G
 from ..ops.decode import KVCache
 from ..ops.paged import DEFAULT_BLOCK_SIZE, PagedKVCache
+from ..utils import flags as _flags
 
 
 @torch.no_grad()
@@ -134,6 +135,18 @@ def dense_weight(w, x):
         raise RuntimeError("a model with quantised weights is inference only: run it under torch.no_grad() "
                            "and without the autograd tape")
     return w.dequant(x.dtype)
+
+
+def cached_linear(w, rows):
+    """The op for the weight products of a decode step or an extend of ``rows`` rows:
+    ``ops.mxfp4_linear`` for an ``ops.Mxfp4Weight`` with more rows than the decode kernels cover
+    and at most ``ops.rows_mxfp4.ROUTED_ROWS`` (the multi-row-tile kernel on the packed image,
+    ops/rows_mxfp4.py; ``FLAGS_mxfp4_rows``), else ``ops.skinny_linear`` -- every other weight
+    and row count takes exactly the calls it took before that kernel existed."""
+    if (isinstance(w, ops.Mxfp4Weight) and ops.skinny.MAX_ROWS < rows <= ops.rows_mxfp4.ROUTED_ROWS
+            and _flags.get("mxfp4_rows")):
+        return ops.mxfp4_linear
+    return ops.skinny_linear
 
 
 def _quantized_state_error(*args, **kwargs):
@@ -338,7 +351,9 @@ class GenerationMixin:
         the same function in another summation order.  One difference: with an fp8 cache
         later chunks attend to the *quantised* earlier chunks, one-shot prefill to the
         unquantised prompt.  With quantised weights every chunk of more than
-        ``ops.skinny.MAX_ROWS`` rows pays one dequantisation per matrix."""
+        ``ops.skinny.MAX_ROWS`` rows pays one dequantisation per matrix -- except an mxfp4
+        model's slices of up to ``ops.rows_mxfp4.ROUTED_ROWS`` rows, which run on the packed
+        image (:func:`cached_linear`)."""
         self._check_generation_supported()
         B, S = input_ids.shape
         paged = getattr(cache, "paged", False)

@@ -23,7 +23,7 @@ import torch
 from .. import ops
 from ..autograd import tape as _tape
 from ..nn import Layer
-from .generation import GenerationMixin, dense_weight, prefill_qkv_attention
+from .generation import GenerationMixin, cached_linear, dense_weight, prefill_qkv_attention
 from .llama import _dt, _param
 
 
@@ -133,26 +133,28 @@ class GPTDecoderLayer(Layer):
             y = ops.layer_norm(x, self.ln1_w, self.ln1_b, eps)
         else:
             y, h = ops.layer_norm(x, self.ln1_w, self.ln1_b, eps, residual=residual)
+        lin = cached_linear(self.qkv_w, x.shape[0] * x.shape[1])
         if prefill:
             qkv_w = dense_weight(self.qkv_w, y)
             packed, a = prefill_qkv_attention(y, qkv_w, self.qkv_b, None, None, self.nh, self.nh)
             ops.kv_append(packed, cache, layer_idx, self.nh, self.nh)
-        elif extend and x.shape[0] * x.shape[1] > ops.skinny.MAX_ROWS:
+        elif extend and x.shape[0] * x.shape[1] > ops.skinny.MAX_ROWS and lin is ops.skinny_linear:
             # extend, many rows: the prefill products around append + extend attention
             qkv = ops.linear(y, dense_weight(self.qkv_w, y), self.qkv_b)
             q = ops.kv_append(qkv, cache, layer_idx, self.nh, self.nh)
             a = ops.extend_attention(q, cache, layer_idx).view(x.shape[0], x.shape[1], -1)
         else:
-            # decode: M = B rows per product, weight-streaming kernels (ops/skinny.py)
-            q = ops.kv_append(ops.skinny_linear(y, self.qkv_w, self.qkv_b), cache, layer_idx, self.nh, self.nh)
+            # decode: M = B rows per product, weight-streaming kernels (ops/skinny.py); an mxfp4
+            # weight with more than 16 rows, extends included: ops/rows_mxfp4.py
+            q = ops.kv_append(lin(y, self.qkv_w, self.qkv_b), cache, layer_idx, self.nh, self.nh)
             if extend:  # T tokens per row at the row's own positions
                 a = ops.extend_attention(q, cache, layer_idx).view(x.shape[0], x.shape[1], -1)
             else:
                 a = ops.decode_attention(q, cache, layer_idx).view(x.shape[0], 1, -1)
-            a = ops.skinny_linear(a, self.out_w, self.out_b)
+            a = lin(a, self.out_w, self.out_b)
             y2, h2 = ops.layer_norm(a, self.ln2_w, self.ln2_b, eps, residual=h)
-            m = ops.skinny_linear(y2, self.fc1_w, self.fc1_b, act="gelu_tanh")
-            return ops.skinny_linear(m, self.fc2_w, self.fc2_b), h2
+            m = lin(y2, self.fc1_w, self.fc1_b, act="gelu_tanh")
+            return lin(m, self.fc2_w, self.fc2_b), h2
         a = ops.linear(a, dense_weight(self.out_w, a), self.out_b)
         y2, h2 = ops.layer_norm(a, self.ln2_w, self.ln2_b, eps, residual=h)
         m = ops.linear_gelu(y2, dense_weight(self.fc1_w, y2), self.fc1_b)

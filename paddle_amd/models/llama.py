@@ -27,7 +27,7 @@ import torch
 from .. import ops
 from ..autograd import tape as _tape
 from ..nn import Layer
-from .generation import GenerationMixin, dense_weight, prefill_qkv_attention
+from .generation import GenerationMixin, cached_linear, dense_weight, prefill_qkv_attention
 
 
 @dataclass
@@ -185,28 +185,30 @@ class LlamaDecoderLayer(Layer):
             y = ops.rms_norm(x, self.input_layernorm, eps)
         else:
             y, h = ops.rms_norm(x, self.input_layernorm, eps, residual=residual)
+        lin = cached_linear(self.qkv_proj, x.shape[0] * x.shape[1])
         if prefill:
             qkv_w = dense_weight(self.qkv_proj, y)
             packed, a = prefill_qkv_attention(y, qkv_w, None, cos, sin, self.nh, self.nkv)
             ops.kv_append(packed, cache, layer_idx, self.nh, self.nkv)
-        elif extend and x.shape[0] * x.shape[1] > ops.skinny.MAX_ROWS:
+        elif extend and x.shape[0] * x.shape[1] > ops.skinny.MAX_ROWS and lin is ops.skinny_linear:
             qkv = ops.linear(y, dense_weight(self.qkv_proj, y))
             q = ops.kv_append(qkv, cache, layer_idx, self.nh, self.nkv, cos, sin)
             a = ops.extend_attention(q, cache, layer_idx).view(x.shape[0], x.shape[1], -1)
         else:
-            # decode: M = B rows per product, weight-streaming kernels (ops/skinny.py)
-            q = ops.kv_append(ops.skinny_linear(y, self.qkv_proj), cache, layer_idx, self.nh, self.nkv, cos, sin)
+            # decode: M = B rows per product, weight-streaming kernels (ops/skinny.py); an mxfp4
+            # weight with more than 16 rows, extends included: ops/rows_mxfp4.py
+            q = ops.kv_append(lin(y, self.qkv_proj), cache, layer_idx, self.nh, self.nkv, cos, sin)
             if extend:
                 a = ops.extend_attention(q, cache, layer_idx).view(x.shape[0], x.shape[1], -1)
             else:
                 a = ops.decode_attention(q, cache, layer_idx).view(x.shape[0], 1, -1)
-            a = ops.skinny_linear(a, self.o_proj)
+            a = lin(a, self.o_proj)
             y2, h2 = ops.rms_norm(a, self.post_attention_layernorm, eps, residual=h)
             if self.mlp_interleaved:
-                hm = ops.skinny_linear(y2, self.gate_up_proj, act="swiglu_interleaved")
+                hm = lin(y2, self.gate_up_proj, act="swiglu_interleaved")
             else:
-                hm = ops.swiglu(ops.skinny_linear(y2, self.gate_up_proj))
-            return ops.skinny_linear(hm, self.down_proj), h2
+                hm = ops.swiglu(lin(y2, self.gate_up_proj))
+            return lin(hm, self.down_proj), h2
         a = ops.linear(a, dense_weight(self.o_proj, a))
         y2, h2 = ops.rms_norm(a, self.post_attention_layernorm, eps, residual=h)
         return self._mlp(y2), h2
@@ -308,7 +310,7 @@ class LlamaForCausalLM(Layer, GenerationMixin):
 
     def _lm_logits(self, y):
         if self.lm_head is not None:
-            return ops.skinny_linear(y, self.lm_head)
+            return cached_linear(self.lm_head, y.numel() // y.shape[-1])(y, self.lm_head)
         return ops.skinny_linear_t(y, self.embed_tokens)
 
 

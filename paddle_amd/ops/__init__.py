@@ -14,6 +14,8 @@ from . import skinny_fp8  # noqa: F401
 from .skinny_fp8 import Fp8Weight, quantize_weight_fp8, skinny_fp8_ok, skinny_fp8_default_splits  # noqa: F401
 from . import skinny_mxfp4  # noqa: F401
 from .skinny_mxfp4 import Mxfp4Weight, quantize_weight_mxfp4, skinny_mxfp4_ok, skinny_mxfp4_default_splits  # noqa: F401
+from . import rows_mxfp4  # noqa: F401
+from .rows_mxfp4 import mxfp4_linear, mxfp4_linear_ok, rows_mxfp4_default_splits  # noqa: F401
 from . import sampling  # noqa: F401
 from .sampling import SamplerState, philox_uniform, sample_step, sample_tokens  # noqa: F401
 from . import speculative  # noqa: F401

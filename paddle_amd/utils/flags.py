@@ -45,6 +45,7 @@ _DEFAULTS = {
     "skinny_gemm": True,  # ops/skinny.py: decode-step GEMMs (M <= 16) on the weight-streaming kernel; off = ops.linear / linear_t
     "skinny_fp8": True,  # ops/skinny_fp8.py: decode-step GEMMs of an Fp8Weight on the e4m3 weight-streaming kernel; off = dequant + the bf16 path
     "skinny_mxfp4": True,  # ops/skinny_mxfp4.py: decode-step GEMMs of an Mxfp4Weight on the MFMA weight-streaming kernel; off = dequant + the bf16 path
+    "mxfp4_rows": True,  # ops/rows_mxfp4.py: GEMMs of an Mxfp4Weight with 17..ROUTED_ROWS rows on the multi-row-tile MFMA kernel; off = dequant + the bf16 path
     "moe_decode": True,  # ops/moe_decode.py: MoE FFN of a decode step (M <= 16) on the expert-streaming kernels; off = the plain-torch definition
     "moe_decode_fp8": True,  # ops/moe_decode.py: the e4m3 expert-streaming kernels for Fp8ExpertWeights; off = the plain-torch definition on dequantised experts
     "fp8_wgrad": False,  # ops/grouped.py: fp8 expert dW (measured slower, profiles/r5_moe_fp8_wgrad_NEGATIVE.md)
