@@ -18,9 +18,11 @@ from dataclasses import dataclass
 import torch
 
 from .. import ops
+from ..autograd import tape as _tape
 from ..distributed.fleet.moe import MoELayer, TopKGate
 from ..nn import Layer
 from ..ops import grouped as _grouped
+from ..ops import grouped_fp8w as _grouped_fp8w
 from ..ops.fp8 import fp8_linear
 from ..ops.fused import param_ready
 from .generation import GenerationMixin, dense_weight, prefill_qkv_attention
@@ -116,7 +118,13 @@ class GroupedSwiGLUExperts(Layer):
             return x
         gate_up, down = self.gate_up, self.down
         if isinstance(gate_up, ops.Fp8ExpertWeights):
-            # quantize_weights(): transient images of this layer's two stacks, gone on return
+            # quantize_weights(): the e4m3 ragged grouped kernels on the codes as stored
+            # (ops/grouped_fp8w.py) for as many sorted rows as they were measured faster at ...
+            lim = _grouped_fp8w.ROUTED_SORTED_ROWS
+            if ((lim is None or x.shape[0] <= lim) and not torch.is_grad_enabled()
+                    and _tape.current() is None and ops.grouped_fp8w_ok(x, gate_up, down)):
+                return ops.grouped_swiglu_mlp_fp8w(x, gate_up, down, counts)
+            # ... else transient images of this layer's two stacks, gone on return
             gate_up, down = dense_weight(gate_up, x), dense_weight(down, x)
         else:
             param_ready(gate_up)
@@ -304,7 +312,9 @@ class ErnieMoEForCausalLM(Layer, GenerationMixin):
         """Attention matrices, the dense and shared MLPs (``Fp8Weight``s on the skinny GEMMs) and
         the grouped expert stacks (``Fp8ExpertWeights`` on ``ops.moe_decode_ffn``).  The router,
         embeddings and norms stay.  Prefill, long extends and decode steps of more than 16 rows
-        run on transient dequantised images, for one MoE layer's two stacks at a time."""
+        run the expert stacks on ``ops.grouped_swiglu_mlp_fp8w`` up to its ``ROUTED_SORTED_ROWS``
+        sorted rows, and beyond that (and every ``Fp8Weight``) on transient dequantised images,
+        for one MoE layer's two stacks at a time."""
         if self.cfg.use_fp8_experts:
             raise NotImplementedError("quantize_weights() with use_fp8_experts=True is not implemented")
         targets = []

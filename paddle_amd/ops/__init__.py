@@ -24,3 +24,5 @@ from . import moe_decode  # noqa: F401
 from .moe_decode import moe_decode_ok, moe_decode_route, moe_decode_ffn, moe_decode_default_splits  # noqa: F401
 from .moe_decode import moe_decode_kernel, Fp8ExpertWeights, quantize_experts_fp8  # noqa: F401
 from .moe_decode import moe_decode_fp8_default_splits  # noqa: F401
+from . import grouped_fp8w  # noqa: F401
+from .grouped_fp8w import grouped_swiglu_mlp_fp8w, grouped_fp8w_ok, grouped_fp8w_kernel  # noqa: F401

@@ -118,6 +118,9 @@ _SIGS = {
     "pa_moe_decode_f8_ws_floats": [_I, _I, _I, _I, _I, _I],
     "pa_moe_decode_ffn_f8": [_P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P],
     "pa_fp8w_dequant_experts": [_P, _P, _P, _P, _L, _L, _L, _L, _P],
+    "pa_moe_rows_f8_const": [_I],
+    "pa_moe_rows_f8_ok": [_I, _I, _I, _I, _L, _P, _P, _P, _P, _P, _P, _P, _P],
+    "pa_moe_rows_f8": [_P, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "pa_sample_ok": [_I, _I, _I, _L, _P],
     "pa_philox_uniform": [ctypes.c_ulonglong, _P, _I, _P, _I, _P],
     "pa_sample": [_I, _P, _L, _I, _I, ctypes.c_ulonglong, _P, _I, _I, _F, _I, _F, _P, _P, _I, _P, _P, _L, _L, _P],
