@@ -25,7 +25,7 @@ from ..ops import grouped as _grouped
 from ..ops import grouped_fp8w as _grouped_fp8w
 from ..ops.fp8 import fp8_linear
 from ..ops.fused import param_ready
-from .generation import GenerationMixin, dense_weight, prefill_qkv_attention
+from .generation import GenerationMixin, cached_linear, dense_weight, prefill_qkv_attention
 from .llama import _dt, _param
 
 
@@ -208,7 +208,8 @@ class ErnieMoEDecoderLayer(Layer):
 
     @staticmethod
     def _skinny_mlp(expert, y2):
-        return ops.skinny_linear(ops.swiglu(ops.skinny_linear(y2, expert.gate_up)), expert.down)
+        lin = cached_linear(expert.gate_up, y2.numel() // y2.shape[-1])
+        return lin(ops.swiglu(lin(y2, expert.gate_up)), expert.down)
 
     def _decode_ffn(self, y2):
         """The FFN of a decode step.  Up to ``ops.moe_decode.ROUTED_ROWS`` rows: the selected
@@ -235,26 +236,30 @@ class ErnieMoEDecoderLayer(Layer):
         """``forward`` for inference with a KV cache, as ``LlamaDecoderLayer.forward_cached``:
         prefill and extends of more than ``ops.skinny.MAX_ROWS`` rows run the training kernels
         and ``MoELayer.forward`` (its balance loss is ignored); a decode step and shorter
-        extends run the weight-streaming kernels and ``ops.moe_decode_ffn``."""
+        extends run the weight-streaming kernels and ``ops.moe_decode_ffn``.  With
+        ``Fp8Weight``s an extend of up to ``ops.rows_fp8.ROUTED_ROWS`` rows takes the decode
+        branch too (``cached_linear``: the matrices on their codes, the MoE FFN as a decode
+        step of that many rows)."""
         eps = self.cfg.rms_norm_eps
         if residual is None:
             h = x
             y = ops.rms_norm(x, self.input_layernorm, eps)
         else:
             y, h = ops.rms_norm(x, self.input_layernorm, eps, residual=residual)
+        lin = cached_linear(self.qkv_proj, x.shape[0] * x.shape[1])
         if prefill:
             packed, a = prefill_qkv_attention(y, dense_weight(self.qkv_proj, y), None, cos, sin, self.nh, self.nkv)
             ops.kv_append(packed, cache, layer_idx, self.nh, self.nkv)
-        elif extend and x.shape[0] * x.shape[1] > ops.skinny.MAX_ROWS:
+        elif extend and x.shape[0] * x.shape[1] > ops.skinny.MAX_ROWS and lin is ops.skinny_linear:
             q = ops.kv_append(ops.linear(y, dense_weight(self.qkv_proj, y)), cache, layer_idx, self.nh, self.nkv, cos, sin)
             a = ops.extend_attention(q, cache, layer_idx).view(x.shape[0], x.shape[1], -1)
         else:
-            q = ops.kv_append(ops.skinny_linear(y, self.qkv_proj), cache, layer_idx, self.nh, self.nkv, cos, sin)
+            q = ops.kv_append(lin(y, self.qkv_proj), cache, layer_idx, self.nh, self.nkv, cos, sin)
             if extend:
                 a = ops.extend_attention(q, cache, layer_idx).view(x.shape[0], x.shape[1], -1)
             else:
                 a = ops.decode_attention(q, cache, layer_idx).view(x.shape[0], 1, -1)
-            a = ops.skinny_linear(a, self.o_proj)
+            a = lin(a, self.o_proj)
             y2, h2 = ops.rms_norm(a, self.post_attention_layernorm, eps, residual=h)
             return self._decode_ffn(y2), h2
         a = ops.linear(a, dense_weight(self.o_proj, a))
@@ -313,8 +318,10 @@ class ErnieMoEForCausalLM(Layer, GenerationMixin):
         the grouped expert stacks (``Fp8ExpertWeights`` on ``ops.moe_decode_ffn``).  The router,
         embeddings and norms stay.  Prefill, long extends and decode steps of more than 16 rows
         run the expert stacks on ``ops.grouped_swiglu_mlp_fp8w`` up to its ``ROUTED_SORTED_ROWS``
-        sorted rows, and beyond that (and every ``Fp8Weight``) on transient dequantised images,
-        for one MoE layer's two stacks at a time."""
+        sorted rows, and beyond that on transient dequantised images, for one MoE layer's two
+        stacks at a time; the ``Fp8Weight``s of a decode step or an extend of 17 to
+        ``ops.rows_fp8.ROUTED_ROWS`` rows run ``ops.fp8_linear`` (``cached_linear``), those of
+        a one-shot prefill a transient image each."""
         if self.cfg.use_fp8_experts:
             raise NotImplementedError("quantize_weights() with use_fp8_experts=True is not implemented")
         targets = []

@@ -36,8 +36,9 @@ in one HIP graph) instead of launching it from Python every token.
 one power-of-two scale per (token, kv head): ops/kv_fp8.py.
 
 ``quantize_weights()`` turns the decoder layers' matrices into ``ops.Fp8Weight``s (e4m3 codes,
-power-of-two column scales): decode steps run them on the fp8 weight-streaming kernel,
-prefill on an exact dequantised image (ops/skinny_fp8.py).
+power-of-two column scales): decode steps run them on the fp8 weight-streaming kernel
+(ops/skinny_fp8.py), decode steps and extends of 17 to ``ops.rows_fp8.ROUTED_ROWS`` rows on the
+multi-row-tile kernel (ops/rows_fp8.py), one-shot prefill on an exact dequantised image.
 ``quantize_weights(fmt="mxfp4")`` does the same with ``ops.Mxfp4Weight``s (e2m1 codes, one
 power-of-two scale per 32 input features: 4.25 bits per weight, ops/skinny_mxfp4.py).
 """
@@ -141,11 +142,16 @@ def cached_linear(w, rows):
     """The op for the weight products of a decode step or an extend of ``rows`` rows:
     ``ops.mxfp4_linear`` for an ``ops.Mxfp4Weight`` with more rows than the decode kernels cover
     and at most ``ops.rows_mxfp4.ROUTED_ROWS`` (the multi-row-tile kernel on the packed image,
-    ops/rows_mxfp4.py; ``FLAGS_mxfp4_rows``), else ``ops.skinny_linear`` -- every other weight
-    and row count takes exactly the calls it took before that kernel existed."""
+    ops/rows_mxfp4.py; ``FLAGS_mxfp4_rows``), ``ops.fp8_linear`` likewise for an
+    ``ops.Fp8Weight`` up to ``ops.rows_fp8.ROUTED_ROWS`` (the kernel on the e4m3 codes as stored,
+    ops/rows_fp8.py; ``FLAGS_fp8_rows``), else ``ops.skinny_linear`` -- every other weight and
+    row count takes exactly the calls it took before those kernels existed."""
     if (isinstance(w, ops.Mxfp4Weight) and ops.skinny.MAX_ROWS < rows <= ops.rows_mxfp4.ROUTED_ROWS
             and _flags.get("mxfp4_rows")):
         return ops.mxfp4_linear
+    if (isinstance(w, ops.Fp8Weight) and ops.skinny.MAX_ROWS < rows <= ops.rows_fp8.ROUTED_ROWS
+            and _flags.get("fp8_rows")):
+        return ops.fp8_linear
     return ops.skinny_linear
 
 
@@ -351,9 +357,9 @@ class GenerationMixin:
         the same function in another summation order.  One difference: with an fp8 cache
         later chunks attend to the *quantised* earlier chunks, one-shot prefill to the
         unquantised prompt.  With quantised weights every chunk of more than
-        ``ops.skinny.MAX_ROWS`` rows pays one dequantisation per matrix -- except an mxfp4
-        model's slices of up to ``ops.rows_mxfp4.ROUTED_ROWS`` rows, which run on the packed
-        image (:func:`cached_linear`)."""
+        ``ops.skinny.MAX_ROWS`` rows pays one dequantisation per matrix -- except slices of up
+        to ``ops.rows_mxfp4.ROUTED_ROWS`` (mxfp4) / ``ops.rows_fp8.ROUTED_ROWS`` (fp8) rows,
+        which run on the packed image / the codes as stored (:func:`cached_linear`)."""
         self._check_generation_supported()
         B, S = input_ids.shape
         paged = getattr(cache, "paged", False)

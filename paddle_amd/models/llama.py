@@ -196,7 +196,7 @@ class LlamaDecoderLayer(Layer):
             a = ops.extend_attention(q, cache, layer_idx).view(x.shape[0], x.shape[1], -1)
         else:
             # decode: M = B rows per product, weight-streaming kernels (ops/skinny.py); an mxfp4
-            # weight with more than 16 rows, extends included: ops/rows_mxfp4.py
+            # or fp8 weight with more than 16 rows, extends included: ops/rows_mxfp4.py, ops/rows_fp8.py
             q = ops.kv_append(lin(y, self.qkv_proj), cache, layer_idx, self.nh, self.nkv, cos, sin)
             if extend:
                 a = ops.extend_attention(q, cache, layer_idx).view(x.shape[0], x.shape[1], -1)

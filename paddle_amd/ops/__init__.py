@@ -16,6 +16,8 @@ from . import skinny_mxfp4  # noqa: F401
 from .skinny_mxfp4 import Mxfp4Weight, quantize_weight_mxfp4, skinny_mxfp4_ok, skinny_mxfp4_default_splits  # noqa: F401
 from . import rows_mxfp4  # noqa: F401
 from .rows_mxfp4 import mxfp4_linear, mxfp4_linear_ok, rows_mxfp4_default_splits  # noqa: F401
+from . import rows_fp8  # noqa: F401
+from .rows_fp8 import fp8_linear, fp8_linear_ok, rows_fp8_default_splits  # noqa: F401
 from . import sampling  # noqa: F401
 from .sampling import SamplerState, philox_uniform, sample_step, sample_tokens  # noqa: F401
 from . import speculative  # noqa: F401

@@ -106,6 +106,10 @@ _SIGS = {
     "pa_gemm_rows_mxfp4_splits": [_I, _I],
     "pa_gemm_rows_mxfp4_ws_floats": [_I, _I, _I],
     "pa_gemm_rows_mxfp4": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _L, _L, _I, _I, _P],
+    "pa_gemm_rows_f8_ok": [_I, _I, _I, _L, _L, _L, _I, _I, _P, _P, _P, _P, _P],
+    "pa_gemm_rows_f8_splits": [_I, _I],
+    "pa_gemm_rows_f8_ws_floats": [_I, _I, _I],
+    "pa_gemm_rows_f8": [_P, _P, _L, _P, _P, _P, _I, _P, _I, _I, _I, _L, _L, _I, _I, _P],
     "pa_moe_decode_ok": [_I, _I, _I, _I, _I, _L, _P, _P, _P, _P],
     "pa_moe_decode_route_ok": [_I, _I, _I, _I, _L, _P, _P],
     "pa_moe_decode_splits": [_I, _I, _I],

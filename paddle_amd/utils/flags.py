@@ -46,6 +46,7 @@ _DEFAULTS = {
     "skinny_fp8": True,  # ops/skinny_fp8.py: decode-step GEMMs of an Fp8Weight on the e4m3 weight-streaming kernel; off = dequant + the bf16 path
     "skinny_mxfp4": True,  # ops/skinny_mxfp4.py: decode-step GEMMs of an Mxfp4Weight on the MFMA weight-streaming kernel; off = dequant + the bf16 path
     "mxfp4_rows": True,  # ops/rows_mxfp4.py: GEMMs of an Mxfp4Weight with 17..ROUTED_ROWS rows on the multi-row-tile MFMA kernel; off = dequant + the bf16 path
+    "fp8_rows": True,  # ops/rows_fp8.py: GEMMs of an Fp8Weight with 17..ROUTED_ROWS rows on the multi-row-tile MFMA kernel on the codes as stored; off = dequant + the bf16 path
     "moe_decode": True,  # ops/moe_decode.py: MoE FFN of a decode step (M <= 16) on the expert-streaming kernels; off = the plain-torch definition
     "moe_decode_fp8": True,  # ops/moe_decode.py: the e4m3 expert-streaming kernels for Fp8ExpertWeights; off = the plain-torch definition on dequantised experts
     "moe_rows_fp8": True,  # ops/grouped_fp8w.py: expert-sorted rows of a quantised MoE layer (more than 16 rows) on the e4m3 ragged grouped MFMA kernels; off = dequant + the bf16 grouped GEMM
