@@ -11,7 +11,10 @@
 //                   of a GQA group share every K / V load; K and V go straight from global
 //                   memory to registers (16 B per lane); the online softmax runs in fp32.
 //                   Each split stores a partial (m, l, acc[D]) with plain stores and a
-//                   second kernel merges the splits and writes bf16.
+//                   second kernel merges the splits and writes bf16.  That kernel serves
+//                   Hq / Hk in {1, 2, 4, 8}; 5, 7 and 9..16 are dispatched to the MFMA kernel
+//                   of attn_decode_gqa.hip (pa_attn_decode_mfma runs it for any ratio up to
+//                   16), which fills the same workspace for the same merge kernel.
 //   pa_kv_append_paged / pa_attn_decode_paged
 //                   the same two kernels over a paged cache: k / v pools
 //                   [num_blocks, block_size, Hk, D] and an int32 block table
@@ -46,7 +49,7 @@
 // shuffles and the four waves through LDS once at the end.
 #include <type_traits>
 
-#include "common.h"
+#include "attn_decode_params.h"
 
 using namespace pa;
 
@@ -55,7 +58,6 @@ namespace dec {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kUnroll = 4;  // keys per lane group in flight (2 * kUnroll 16-byte loads per lane)
-constexpr int kMaxSplits = 64;
 constexpr float kE4M3Max = 448.f;
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -237,24 +239,6 @@ __global__ void i32_add_kernel(int* x, int n, int inc) {
 }
 
 // ------------------------------------------------------------------ decode attention
-struct DecodeParams {
-  const u16* q;
-  long qsb, qsh;  // element strides of q [B, 1, Hq, D] over b and head
-  const u16* kc;
-  const u16* vc;
-  const int* kv_len;
-  float* ws;  // [B, Hq, ns, 2] (m, l) then [B, Hq, ns, D] acc
-  u16* o;     // [B, 1, Hq, D] contiguous
-  int B, S_max, Hq, Hk, ns;
-  float scale_log2;  // scale * log2(e): scores live in the log2 domain
-  // paged only: kc / vc are pools [num_blocks, 1 << bs_shift, Hk, D]
-  const int* table;  // [B, max_blocks]
-  int max_blocks, num_blocks, bs_shift;
-  // e4m3 only: kc / vc hold one byte per element, ks / vs one scale per (slot, kv head)
-  const float* ks;
-  const float* vs;
-};
-
 // The 8 elements of a key row one lane holds, as floats.  bf16: the bits shifted up.
 // e4m3: cvt(code) * scale, exact for the append's power-of-two scales (4 significant bits,
 // exponent within [-109, 109]), so the arithmetic downstream sees what a bf16 cache
@@ -594,13 +578,14 @@ static void launch_append(const AppendParams& p, bool f8, hipStream_t st) {
 }
 
 template <int D, bool Paged, bool F8>
-static void launch_decode(const DecodeParams& p, hipStream_t st) {
+static void launch_decode(const DecodeParams& p, bool mfma, hipStream_t st) {
   const dim3 grid(p.ns, p.Hk, p.B);
-  switch (p.Hq / p.Hk) {
+  switch (mfma ? 0 : p.Hq / p.Hk) {
     case 1: hipLaunchKernelGGL((attn_decode_kernel<D, 1, Paged, F8>), grid, dim3(kThreads), 0, st, p); break;
     case 2: hipLaunchKernelGGL((attn_decode_kernel<D, 2, Paged, F8>), grid, dim3(kThreads), 0, st, p); break;
     case 4: hipLaunchKernelGGL((attn_decode_kernel<D, 4, Paged, F8>), grid, dim3(kThreads), 0, st, p); break;
-    default: hipLaunchKernelGGL((attn_decode_kernel<D, 8, Paged, F8>), grid, dim3(kThreads), 0, st, p); break;
+    case 8: hipLaunchKernelGGL((attn_decode_kernel<D, 8, Paged, F8>), grid, dim3(kThreads), 0, st, p); break;
+    default: launch_decode_gqa(p, D, st); break;  // the MFMA kernel: any ratio up to 16
   }
   hipLaunchKernelGGL((attn_decode_merge_kernel<D>), dim3(p.B * p.Hq), dim3(D), 0, st, p);
 }
@@ -724,15 +709,38 @@ PA_EXPORT int pa_i32_add(int* x, int n, int inc, hipStream_t st) {
   PA_LAUNCH_CHECK();
 }
 
-// Whether pa_attn_decode takes this problem (else the caller runs its reference path).
-PA_EXPORT int pa_attn_decode_ok(int B, int S_max, int Hq, int Hk, int D, int num_splits, const long* qstrides /*2*/) {
+// The rules every decode attention shares: the grid limits, the head sizes, a GQA group of
+// up to 16 query heads, the split range, 16-byte q rows and (block_size != 0) a paged cache
+// with a block size of 16..256 (a power of two) and a table that covers S_max.
+static int decode_common_ok(int B, int S_max, int Hq, int Hk, int D, int num_splits, const long* qstrides,
+                            int block_size, int max_blocks, int num_blocks) {
   if (B <= 0 || B > 65535 || S_max <= 0 || Hq <= 0 || Hk <= 0 || Hk > 65535 || Hq % Hk) return 0;
   if (D != 64 && D != 128) return 0;
-  const int g = Hq / Hk;
-  if (g != 1 && g != 2 && g != 4 && g != 8) return 0;
+  if (Hq / Hk > 16) return 0;
   if (num_splits < 1 || num_splits > dec::kMaxSplits) return 0;
   if (qstrides[0] % 8 || qstrides[1] % 8) return 0;
+  if (block_size != 0) {
+    const int shift = paged_block_shift(block_size);
+    if (shift < 0 || num_blocks <= 0 || max_blocks <= 0) return 0;
+    if (((long)max_blocks << shift) < (long)S_max) return 0;
+  }
   return 1;
+}
+
+// Whether pa_attn_decode_mfma takes this problem: every ratio 1 <= Hq / Hk <= 16.
+// block_size 0: a contiguous cache (max_blocks and num_blocks are ignored).
+PA_EXPORT int pa_attn_decode_mfma_ok(int B, int S_max, int Hq, int Hk, int D, int num_splits,
+                                     const long* qstrides /*2*/, int block_size, int max_blocks, int num_blocks) {
+  return decode_common_ok(B, S_max, Hq, Hk, D, num_splits, qstrides, block_size, max_blocks, num_blocks);
+}
+
+// Whether pa_attn_decode takes this problem (else the caller runs its reference path).
+// Ratios 1, 2, 4, 8 run attn_decode_kernel; 5, 7 and 9..16 the MFMA kernel of
+// attn_decode_gqa.hip.  3 and 6 are refused here although that kernel takes them.
+PA_EXPORT int pa_attn_decode_ok(int B, int S_max, int Hq, int Hk, int D, int num_splits, const long* qstrides /*2*/) {
+  if (!decode_common_ok(B, S_max, Hq, Hk, D, num_splits, qstrides, 0, 0, 0)) return 0;
+  const int g = Hq / Hk;
+  return g != 3 && g != 6;
 }
 
 // Split count from the launch shape alone (never from kv_len: no host read per step):
@@ -771,7 +779,7 @@ PA_EXPORT int pa_attn_decode_paged_f8_ok(int B, int S_max, int Hq, int Hk, int D
 static int decode_launch(const void* q, const long* qstrides, const void* k, const void* v, const float* k_scale,
                          const float* v_scale, const int* table, int max_blocks, int num_blocks, int block_size,
                          const int* kv_len, void* o, float* ws, int B, int S_max, int Hq, int Hk, int D, float scale,
-                         int num_splits, hipStream_t st) {
+                         int num_splits, bool mfma, hipStream_t st) {
   dec::DecodeParams p;
   p.q = (const u16*)q; p.qsb = qstrides[0]; p.qsh = qstrides[1];
   p.kc = (const u16*)k; p.vc = (const u16*)v; p.kv_len = kv_len;
@@ -784,18 +792,18 @@ static int decode_launch(const void* q, const long* qstrides, const void* k, con
   const bool f8 = k_scale != nullptr;
   if (table != nullptr) {
     if (f8) {
-      if (D == 128) dec::launch_decode<128, true, true>(p, st);
-      else dec::launch_decode<64, true, true>(p, st);
+      if (D == 128) dec::launch_decode<128, true, true>(p, mfma, st);
+      else dec::launch_decode<64, true, true>(p, mfma, st);
     } else {
-      if (D == 128) dec::launch_decode<128, true, false>(p, st);
-      else dec::launch_decode<64, true, false>(p, st);
+      if (D == 128) dec::launch_decode<128, true, false>(p, mfma, st);
+      else dec::launch_decode<64, true, false>(p, mfma, st);
     }
   } else if (f8) {
-    if (D == 128) dec::launch_decode<128, false, true>(p, st);
-    else dec::launch_decode<64, false, true>(p, st);
+    if (D == 128) dec::launch_decode<128, false, true>(p, mfma, st);
+    else dec::launch_decode<64, false, true>(p, mfma, st);
   } else {
-    if (D == 128) dec::launch_decode<128, false, false>(p, st);
-    else dec::launch_decode<64, false, false>(p, st);
+    if (D == 128) dec::launch_decode<128, false, false>(p, mfma, st);
+    else dec::launch_decode<64, false, false>(p, mfma, st);
   }
   PA_LAUNCH_CHECK();
 }
@@ -805,7 +813,7 @@ PA_EXPORT int pa_attn_decode(const void* q, const long* qstrides /*2: b, head*/,
                              int Hk, int D, float scale, int num_splits, hipStream_t st) {
   if (!pa_attn_decode_ok(B, S_max, Hq, Hk, D, num_splits, qstrides)) return (int)hipErrorInvalidValue;
   return decode_launch(q, qstrides, k_cache, v_cache, nullptr, nullptr, nullptr, 0, 0, 0, kv_len, o, ws, B, S_max, Hq,
-                       Hk, D, scale, num_splits, st);
+                       Hk, D, scale, num_splits, false, st);
 }
 
 // pa_attn_decode over a paged cache (k_pool / v_pool [num_blocks, block_size, Hk, D],
@@ -820,7 +828,7 @@ PA_EXPORT int pa_attn_decode_paged(const void* q, const long* qstrides /*2: b, h
       table == nullptr)
     return (int)hipErrorInvalidValue;
   return decode_launch(q, qstrides, k_pool, v_pool, nullptr, nullptr, table, max_blocks, num_blocks, block_size,
-                       kv_len, o, ws, B, S_max, Hq, Hk, D, scale, num_splits, st);
+                       kv_len, o, ws, B, S_max, Hq, Hk, D, scale, num_splits, false, st);
 }
 
 // pa_attn_decode over an e4m3 cache (k_codes / v_codes [B, S_max, Hk, D] one byte each,
@@ -833,7 +841,7 @@ PA_EXPORT int pa_attn_decode_f8(const void* q, const long* qstrides /*2: b, head
   if (!pa_attn_decode_f8_ok(B, S_max, Hq, Hk, D, num_splits, qstrides) || k_scale == nullptr || v_scale == nullptr)
     return (int)hipErrorInvalidValue;
   return decode_launch(q, qstrides, k_codes, v_codes, k_scale, v_scale, nullptr, 0, 0, 0, kv_len, o, ws, B, S_max,
-                       Hq, Hk, D, scale, num_splits, st);
+                       Hq, Hk, D, scale, num_splits, false, st);
 }
 
 // pa_attn_decode_f8 over a paged e4m3 cache (codes [num_blocks, block_size, Hk, D], scales
@@ -847,5 +855,23 @@ PA_EXPORT int pa_attn_decode_paged_f8(const void* q, const long* qstrides /*2: b
       table == nullptr || k_scale == nullptr || v_scale == nullptr)
     return (int)hipErrorInvalidValue;
   return decode_launch(q, qstrides, k_codes, v_codes, k_scale, v_scale, table, max_blocks, num_blocks, block_size,
-                       kv_len, o, ws, B, S_max, Hq, Hk, D, scale, num_splits, st);
+                       kv_len, o, ws, B, S_max, Hq, Hk, D, scale, num_splits, false, st);
+}
+
+// The MFMA kernel of attn_decode_gqa.hip whatever the ratio (1 <= Hq / Hk <= 16), followed by
+// the merge kernel.  k_scale / v_scale null: a bf16 cache; table null: a contiguous one
+// (max_blocks, num_blocks and block_size are ignored).  ws as for pa_attn_decode.
+PA_EXPORT int pa_attn_decode_mfma(const void* q, const long* qstrides /*2: b, head*/, const void* k, const void* v,
+                                  const float* k_scale, const float* v_scale, const int* table, int max_blocks,
+                                  int num_blocks, int block_size, const int* kv_len, void* o,
+                                  float* ws /*B*Hq*num_splits*(D+2)*/, int B, int S_max, int Hq, int Hk, int D,
+                                  float scale, int num_splits, hipStream_t st) {
+  const bool paged = table != nullptr;
+  if (paged && block_size == 0) return (int)hipErrorInvalidValue;
+  if (!pa_attn_decode_mfma_ok(B, S_max, Hq, Hk, D, num_splits, qstrides, paged ? block_size : 0, max_blocks,
+                              num_blocks) ||
+      (k_scale == nullptr) != (v_scale == nullptr))
+    return (int)hipErrorInvalidValue;
+  return decode_launch(q, qstrides, k, v, k_scale, v_scale, table, max_blocks, num_blocks, block_size, kv_len, o, ws,
+                       B, S_max, Hq, Hk, D, scale, num_splits, true, st);
 }

@@ -2,7 +2,8 @@
 per row) and ``extend_attention`` (T new tokens per row, causal inside the chunk).
 
 GPU bf16 tensors run the gfx950 kernels of ``csrc/kernels/attn_decode.hip`` (and
-``csrc/kernels/attn_extend.hip``: the MFMA kernel behind ``extend_attention``); CPU
+``csrc/kernels/attn_decode_gqa.hip``: the MFMA decode attention for 5, 7 and 9..16 query heads
+per KV head; ``csrc/kernels/attn_extend.hip``: the MFMA kernel behind ``extend_attention``); CPU
 tensors, other dtypes and shapes the kernels do not cover run the plain-torch
 definitions below (the fp32 oracle of the GPU tests).  These are inference ops: they
 record nothing on the tape and run under ``torch.no_grad()``.
@@ -297,9 +298,12 @@ def decode_attention(q, cache, layer: int, scale: float | None = None, num_split
     to ``cache.lens + 1`` -- the token ``kv_append`` has just written, before
     ``cache.advance()``.  Returns o [B, 1, Hq, D].
 
-    On the GPU (bf16, D in {64, 128}, Hq/Hk in {1, 2, 4, 8}) the key axis is cut into
-    ``num_splits`` ranges that run as separate workgroups and are merged by a second
-    kernel; the result is bit-identical from run to run for a given ``num_splits``.  A
+    On the GPU (bf16, D in {64, 128}, Hq/Hk in {1, 2, 4, 5, 7, 8, 9..16}) the key axis is cut
+    into ``num_splits`` ranges that run as separate workgroups and are merged by a second
+    kernel; the result is bit-identical from run to run for a given ``num_splits``.  Ratios 1,
+    2, 4 and 8 run the VALU kernel of ``attn_decode.hip``; 5, 7 and 9..16 the MFMA kernel of
+    ``attn_decode_gqa.hip`` (both products on the matrix unit, P rounded to bf16 once), with the
+    same bit equalities between layouts and storage types; 3 and 6 take the reference.  A
     quantised cache runs the e4m3 instantiation of the same kernel (the bits of the bf16 one
     over ``cache.dequant(layer)``); elsewhere it is the reference over ``cache.dequant(layer)``."""
     B, Tq, Hq, D = q.shape
@@ -334,6 +338,32 @@ def decode_attention(q, cache, layer: int, scale: float | None = None, num_split
             return o
     k, v = cache.dequant(layer)
     return _decode_attention_ref(q, k, v, kv_len, float(scale))
+
+
+def _decode_mfma_kernel(q, cache, layer, scale, num_splits, kv_len, out=None):
+    """Launch pa_attn_decode_mfma (``csrc/kernels/attn_decode_gqa.hip``) whatever the routing of
+    ``decode_attention`` says, for either layout and storage type; None when
+    ``pa_attn_decode_mfma_ok`` refuses.  ``out``: a contiguous [B, 1, Hq, D] buffer to write."""
+    B, _, Hq, D = q.shape
+    Hk, S_max = cache.num_kv_heads, cache.max_len
+    paged = getattr(cache, "paged", False)
+    if not (q.is_cuda and q.dtype == torch.bfloat16 and cache.dtype == torch.bfloat16 and q.stride(-1) == 1
+            and _aligned16(q) and kv_len.is_cuda and kv_len.dtype == torch.int32 and kv_len.is_contiguous()
+            and Hk > 0 and Hq % Hk == 0):
+        return None
+    ns = default_num_splits(B, Hk, S_max) if num_splits is None else int(num_splits)
+    qst = ctypes_long_array([q.stride(0), q.stride(2)])
+    geom = (cache.block_size, cache.max_blocks, cache.num_blocks) if paged else (0, 0, 0)
+    if not N.lib().pa_attn_decode_mfma_ok(B, S_max, Hq, Hk, D, ns, qst, *geom):
+        return None
+    o = torch.empty(B, 1, Hq, D, dtype=q.dtype, device=q.device) if out is None else out
+    ws = torch.empty(B * Hq * ns * (D + 2), dtype=torch.float32, device=q.device)
+    ksc = cache.k_scale[layer] if cache.quantized else None
+    vsc = cache.v_scale[layer] if cache.quantized else None
+    N.call("pa_attn_decode_mfma", N.ptr(q), qst, N.ptr(cache.k[layer]), N.ptr(cache.v[layer]), N.ptr(ksc),
+           N.ptr(vsc), N.ptr(cache.block_table) if paged else None, geom[1], geom[2], geom[0], N.ptr(kv_len),
+           N.ptr(o), N.ptr(ws), B, S_max, Hq, Hk, D, float(scale), ns, N.stream())
+    return o
 
 
 def _extend_attention_ref(q, k, v, base_len, scale):
@@ -398,7 +428,8 @@ def extend_attention(q, cache, layer: int, scale: float | None = None, num_split
     row ``rows[i]``; inside ``cache.prefilling(rows)`` the mapping comes from the scope.  An
     explicit ``base_len`` is indexed by q row.
 
-    On the GPU (bf16 q, D in {64, 128}, Hq/Hk in {1, 2, 4, 8}) this is ``pa_attn_extend`` of
+    On the GPU (bf16 q, D in {64, 128}, Hq/Hk in {1, 2, 4, 8}: not the ratios 5, 7 and 9..16
+    that ``decode_attention`` also takes) this is ``pa_attn_extend`` of
     ``csrc/kernels/attn_extend.hip``: both products on the bf16 MFMA, the key range cut into
     ``num_splits`` ranges (``default_extend_splits``: from the launch shape only), bit-identical
     from run to run.  The paged instantiation returns the bits of the contiguous one for equal
