@@ -11,6 +11,12 @@
 //                   cache row rows[i]; base_len is indexed by the q row.  A query without a
 //                   visible key gives zeros.  o [B, T, Hq, D] bf16, contiguous.
 //
+// Routing.  Hq / Hk of 1, 2, 4 and 8 run attn_extend_kernel below, one instantiation per ratio;
+// 5, 7 and 9..16 run the run-time-ratio kernel of attn_extend_gqa.hip, which shares Params, the
+// tile geometry, the row-address policy (attn_extend_params.h) and the merge kernel below, and
+// which pa_attn_extend_gqa runs for every ratio up to 16.  3 and 6 are refused by
+// pa_attn_extend (that kernel takes them).
+//
 // Tiling.  The G = Hq / Hk query heads of a GQA group and 64 / G consecutive tokens are
 // stacked into 64 rows of M; one workgroup of four waves owns (such a query tile, kv head,
 // row, split) and every wave 16 of the rows.  Keys are visited in tiles of 64.  A K / V tile
@@ -43,56 +49,11 @@
 // from run to run.  Every cache-row address is computed in 64 bits.
 #include <type_traits>
 
-#include "common.h"
+#include "attn_extend_params.h"
 
 using namespace pa;
 
 namespace ext {
-
-constexpr int kThreads = 256;
-constexpr int kBM = 64;  // stacked query rows (token x head of the group) per workgroup
-constexpr int kBN = 64;  // keys per tile
-constexpr int kMaxSplits = 64;
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-struct Params {
-  const u16* q;
-  long qsb, qst, qsh;  // element strides of q [B, T, Hq, D] over b, t and head
-  const void* kc;
-  const void* vc;
-  const float* ks;  // e4m3 only: one scale per (slot, kv head)
-  const float* vs;
-  const int* base_len;  // [B]
-  const int* rows;      // [B] q row -> cache row, or null: the identity (paged only)
-  const int* table;     // [Bc, max_blocks] (paged only)
-  float* ws;            // num_splits > 1: [B*T*Hq, ns, 2] (m, l) then [B*T*Hq, ns, D] acc
-  u16* o;
-  int B, Bc, T, S_max, Hq, Hk, ns, qtiles;
-  int max_blocks, num_blocks, bs_shift;
-  float scale_log2;  // scale * log2(e)
-};
-
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-// 8 elements of a cache row as bf16 bits.  e4m3: cvt(code) * scale, exact in bf16.
-__device__ __forceinline__ u16x8 row_bf16(const u16x8& r, float) { return r; }
-__device__ __forceinline__ u16x8 row_bf16(const u32x2& r, float sc) {
-  u16x8 o;
-#pragma unroll
-  for (int d = 0; d < 2; ++d) {
-    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[d], false) * sc;
-    const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[d], true) * sc;
-    o[4 * d] = f2bf(lo.x);
-    o[4 * d + 1] = f2bf(lo.y);
-    o[4 * d + 2] = f2bf(hi.x);
-    o[4 * d + 3] = f2bf(hi.y);
-  }
-  return o;
-}
 
 template <int D, int G, bool Paged, bool F8>
 __global__ __launch_bounds__(kThreads) void attn_extend_kernel(Params p) {
@@ -164,7 +125,6 @@ __global__ __launch_bounds__(kThreads) void attn_extend_kernel(Params p) {
   const Elt* kb = reinterpret_cast<const Elt*>(p.kc) + (long)hk * D;
   const Elt* vb = reinterpret_cast<const Elt*>(p.vc) + (long)hk * D;
   const int* trow = Paged ? p.table + (long)cb * p.max_blocks : nullptr;
-  const long bmask = Paged ? (1L << p.bs_shift) - 1 : 0;
 
   Vec kr[NCH], vr[NCH];
   float ksc[NCH], vsc[NCH];
@@ -190,14 +150,9 @@ __global__ __launch_bounds__(kThreads) void attn_extend_kernel(Params p) {
       const int c = id % CPR;
       const long key = k0 + id / CPR;
       bool ok = key < end;
-      long slot;
-      if constexpr (Paged) {
-        const int blk = blkn[i];  // fetched by the call before this one
-        ok = ok && (unsigned)blk < (unsigned)p.num_blocks;  // no block: masked, never dereferenced
-        slot = ((long)blk << p.bs_shift) + (key & bmask);
-      } else {
-        slot = (long)cb * p.S_max + key;
-      }
+      const int blk = Paged ? blkn[i] : 0;  // fetched by the call before this one
+      if constexpr (Paged) ok = ok && (unsigned)blk < (unsigned)p.num_blocks;  // no block: masked, never dereferenced
+      const long slot = cache_slot<Paged>(p, cb, blk, key);
       okr[i] = ok;
       Vec kz, vz;
 #pragma unroll
@@ -385,18 +340,18 @@ PA_EXPORT int pa_i32_add_rows(int* x, const int* inc, int n, hipStream_t st) {
   PA_LAUNCH_CHECK();
 }
 
-// Whether pa_attn_extend takes this problem (else the caller runs its reference path).
+// Whether pa_attn_extend_gqa takes this problem: every ratio 1 <= Hq / Hk <= 16.
 // block_size 0: a contiguous cache (max_blocks and num_blocks are ignored).
-PA_EXPORT int pa_attn_extend_ok(int B, int T, int S_max, int Hq, int Hk, int D, int num_splits,
-                                const long* qstrides /*3: b, t, head*/, int block_size, int max_blocks,
-                                int num_blocks) {
+PA_EXPORT int pa_attn_extend_gqa_ok(int B, int T, int S_max, int Hq, int Hk, int D, int num_splits,
+                                    const long* qstrides /*3: b, t, head*/, int block_size, int max_blocks,
+                                    int num_blocks) {
   if (B <= 0 || B > 65535 || T <= 0 || S_max <= 0 || Hq <= 0 || Hk <= 0 || Hk > 65535 || Hq % Hk) return 0;
   if (D != 64 && D != 128) return 0;
   const int g = Hq / Hk;
-  if (g != 1 && g != 2 && g != 4 && g != 8) return 0;
+  if (g > ext::kMaxGroup) return 0;
   if (num_splits < 1 || num_splits > ext::kMaxSplits) return 0;
   if (qstrides[0] % 8 || qstrides[1] % 8 || qstrides[2] % 8) return 0;
-  const long qtiles = ((long)T * g + ext::kBM - 1) / ext::kBM;
+  const long qtiles = ext::query_tiles(T, g);
   if (qtiles * num_splits > 0x7FFFFFFFL || (long)B * T * Hq > 0x7FFFFFFFL) return 0;
   if (block_size != 0) {
     const int shift = ext::block_shift(block_size);
@@ -404,6 +359,18 @@ PA_EXPORT int pa_attn_extend_ok(int B, int T, int S_max, int Hq, int Hk, int D, 
     if (((long)max_blocks << shift) < (long)S_max) return 0;
   }
   return 1;
+}
+
+// Whether pa_attn_extend takes this problem (else the caller runs its reference path): the
+// ratios 1, 2, 4, 8 (attn_extend_kernel) and 5, 7, 9..16 (attn_extend_gqa.hip).  3 and 6 are
+// refused here although that kernel takes them.
+PA_EXPORT int pa_attn_extend_ok(int B, int T, int S_max, int Hq, int Hk, int D, int num_splits,
+                                const long* qstrides /*3: b, t, head*/, int block_size, int max_blocks,
+                                int num_blocks) {
+  if (!pa_attn_extend_gqa_ok(B, T, S_max, Hq, Hk, D, num_splits, qstrides, block_size, max_blocks, num_blocks))
+    return 0;
+  const int g = Hq / Hk;
+  return g != 3 && g != 6;
 }
 
 // Split count from the launch shape alone (never from the lengths: no host read): enough
@@ -418,6 +385,62 @@ PA_EXPORT int pa_attn_extend_splits(int B, int Hk, int T, int S_max) {
   return want < 1 ? 1 : (int)want;
 }
 
+namespace ext {
+
+// The checks and the launch behind both entry points.  gqa: attn_extend_gqa.hip whatever the
+// ratio; otherwise 1 / 2 / 4 / 8 keep attn_extend_kernel and the other ratios go there.
+static int run(bool gqa, const void* q, const long* qstrides, const void* k, const void* v, const float* k_scale,
+               const float* v_scale, const int* table, int max_blocks, int num_blocks, int block_size,
+               const int* rows, const int* base_len, void* o, float* ws, int B, int Bc, int T, int S_max, int Hq,
+               int Hk, int D, float scale, int num_splits, hipStream_t st) {
+  const bool paged = table != nullptr;
+  if (!(gqa ? pa_attn_extend_gqa_ok : pa_attn_extend_ok)(B, T, S_max, Hq, Hk, D, num_splits, qstrides,
+                                                         paged ? block_size : 0, max_blocks, num_blocks))
+    return (int)hipErrorInvalidValue;
+  if (paged && block_size == 0) return (int)hipErrorInvalidValue;
+  if (!paged && rows != nullptr) return (int)hipErrorInvalidValue;
+  if (paged && (Bc <= 0 || (rows == nullptr && B != Bc))) return (int)hipErrorInvalidValue;
+  if ((k_scale == nullptr) != (v_scale == nullptr) || base_len == nullptr) return (int)hipErrorInvalidValue;
+  if (num_splits > 1 && ws == nullptr) return (int)hipErrorInvalidValue;
+  Params p;
+  p.q = (const u16*)q; p.qsb = qstrides[0]; p.qst = qstrides[1]; p.qsh = qstrides[2];
+  p.kc = k; p.vc = v; p.ks = k_scale; p.vs = v_scale;
+  p.base_len = base_len; p.rows = rows; p.table = table;
+  p.ws = ws; p.o = (u16*)o;
+  p.B = B; p.Bc = paged ? Bc : B; p.T = T; p.S_max = S_max; p.Hq = Hq; p.Hk = Hk; p.ns = num_splits;
+  const int g = Hq / Hk;
+  p.qtiles = query_tiles(T, g);
+  p.max_blocks = max_blocks; p.num_blocks = num_blocks;
+  p.bs_shift = paged ? block_shift(block_size) : 0;
+  p.scale_log2 = scale * 1.4426950408889634f;
+  const bool f8 = k_scale != nullptr;
+  if (gqa || (g != 1 && g != 2 && g != 4 && g != 8)) {
+    launch_extend_gqa(p, D, st);
+    if (p.ns > 1) {
+      const dim3 grid((unsigned)((long)B * T * Hq));
+      if (D == 128) hipLaunchKernelGGL((attn_extend_merge_kernel<128>), grid, dim3(128), 0, st, p);
+      else hipLaunchKernelGGL((attn_extend_merge_kernel<64>), grid, dim3(64), 0, st, p);
+    }
+  } else if (paged) {
+    if (f8) {
+      if (D == 128) launch<128, true, true>(p, st);
+      else launch<64, true, true>(p, st);
+    } else {
+      if (D == 128) launch<128, true, false>(p, st);
+      else launch<64, true, false>(p, st);
+    }
+  } else if (f8) {
+    if (D == 128) launch<128, false, true>(p, st);
+    else launch<64, false, true>(p, st);
+  } else {
+    if (D == 128) launch<128, false, false>(p, st);
+    else launch<64, false, false>(p, st);
+  }
+  PA_LAUNCH_CHECK();
+}
+
+}  // namespace ext
+
 // ws: B * T * Hq * num_splits * (D + 2) floats when num_splits > 1, unused (may be null) otherwise.
 // table null: contiguous (rows must be null, Bc is ignored).  k_scale null: a bf16 cache.
 PA_EXPORT int pa_attn_extend(const void* q, const long* qstrides /*3: b, t, head*/, const void* k, const void* v,
@@ -425,40 +448,18 @@ PA_EXPORT int pa_attn_extend(const void* q, const long* qstrides /*3: b, t, head
                              int num_blocks, int block_size, const int* rows, const int* base_len, void* o,
                              float* ws, int B, int Bc, int T, int S_max, int Hq, int Hk, int D, float scale,
                              int num_splits, hipStream_t st) {
-  const bool paged = table != nullptr;
-  if (!pa_attn_extend_ok(B, T, S_max, Hq, Hk, D, num_splits, qstrides, paged ? block_size : 0, max_blocks,
-                         num_blocks))
-    return (int)hipErrorInvalidValue;
-  if (paged && block_size == 0) return (int)hipErrorInvalidValue;
-  if (!paged && rows != nullptr) return (int)hipErrorInvalidValue;
-  if (paged && (Bc <= 0 || (rows == nullptr && B != Bc))) return (int)hipErrorInvalidValue;
-  if ((k_scale == nullptr) != (v_scale == nullptr) || base_len == nullptr) return (int)hipErrorInvalidValue;
-  if (num_splits > 1 && ws == nullptr) return (int)hipErrorInvalidValue;
-  ext::Params p;
-  p.q = (const u16*)q; p.qsb = qstrides[0]; p.qst = qstrides[1]; p.qsh = qstrides[2];
-  p.kc = k; p.vc = v; p.ks = k_scale; p.vs = v_scale;
-  p.base_len = base_len; p.rows = rows; p.table = table;
-  p.ws = ws; p.o = (u16*)o;
-  p.B = B; p.Bc = paged ? Bc : B; p.T = T; p.S_max = S_max; p.Hq = Hq; p.Hk = Hk; p.ns = num_splits;
-  p.qtiles = (int)(((long)T * (Hq / Hk) + ext::kBM - 1) / ext::kBM);
-  p.max_blocks = max_blocks; p.num_blocks = num_blocks;
-  p.bs_shift = paged ? ext::block_shift(block_size) : 0;
-  p.scale_log2 = scale * 1.4426950408889634f;
-  const bool f8 = k_scale != nullptr;
-  if (paged) {
-    if (f8) {
-      if (D == 128) ext::launch<128, true, true>(p, st);
-      else ext::launch<64, true, true>(p, st);
-    } else {
-      if (D == 128) ext::launch<128, true, false>(p, st);
-      else ext::launch<64, true, false>(p, st);
-    }
-  } else if (f8) {
-    if (D == 128) ext::launch<128, false, true>(p, st);
-    else ext::launch<64, false, true>(p, st);
-  } else {
-    if (D == 128) ext::launch<128, false, false>(p, st);
-    else ext::launch<64, false, false>(p, st);
-  }
-  PA_LAUNCH_CHECK();
+  return ext::run(false, q, qstrides, k, v, k_scale, v_scale, table, max_blocks, num_blocks, block_size, rows,
+                  base_len, o, ws, B, Bc, T, S_max, Hq, Hk, D, scale, num_splits, st);
+}
+
+// The kernel of attn_extend_gqa.hip whatever the ratio (1 <= Hq / Hk <= 16), followed by the
+// merge kernel above: pa_attn_extend's arguments, workspace and contract.  At 1 / 2 / 4 / 8 it
+// returns the bits of pa_attn_extend.
+PA_EXPORT int pa_attn_extend_gqa(const void* q, const long* qstrides /*3: b, t, head*/, const void* k,
+                                 const void* v, const float* k_scale, const float* v_scale, const int* table,
+                                 int max_blocks, int num_blocks, int block_size, const int* rows,
+                                 const int* base_len, void* o, float* ws, int B, int Bc, int T, int S_max, int Hq,
+                                 int Hk, int D, float scale, int num_splits, hipStream_t st) {
+  return ext::run(true, q, qstrides, k, v, k_scale, v_scale, table, max_blocks, num_blocks, block_size, rows,
+                  base_len, o, ws, B, Bc, T, S_max, Hq, Hk, D, scale, num_splits, st);
 }

@@ -272,8 +272,8 @@ class ErnieMoEForCausalLM(Layer, GenerationMixin):
     ``ops.decode_attention`` takes 1, 2, 4, 5, 7, 8 and 9..16 query heads per KV head, so the
     20 / 4 heads of the ernie-moe-21b-a3b preset (5 per KV head) decode on the MFMA kernel of
     ``csrc/kernels/attn_decode_gqa.hip`` and ``graph=True`` works.  ``ops.extend_attention`` takes
-    1, 2, 4 or 8 only: ``extend``, chunked prefill and a speculative verify pass of that preset run
-    the plain-torch attention, which reads the lengths from the device."""
+    the same ratios: ``extend``, chunked prefill and a speculative verify pass of that preset run
+    the kernel of ``csrc/kernels/attn_extend_gqa.hip`` and read no length from the device."""
 
     def __init__(self, cfg: ErnieMoEConfig, device=None, ep_group=None):
         super().__init__("ernie_moe")

@@ -73,6 +73,9 @@ _SIGS = {
     "pa_attn_extend_splits": [_I, _I, _I, _I],
     "pa_attn_extend": [_P, _LP, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _I,
                        _P],
+    "pa_attn_extend_gqa_ok": [_I, _I, _I, _I, _I, _I, _I, _LP, _I, _I, _I],
+    "pa_attn_extend_gqa": [_P, _LP, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F,
+                           _I, _P],
     "pa_attn_decode_ok": [_I, _I, _I, _I, _I, _I, _LP],
     "pa_attn_decode_splits": [_I, _I, _I],
     "pa_attn_decode": [_P, _LP, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],

@@ -3,7 +3,8 @@ per row) and ``extend_attention`` (T new tokens per row, causal inside the chunk
 
 GPU bf16 tensors run the gfx950 kernels of ``csrc/kernels/attn_decode.hip`` (and
 ``csrc/kernels/attn_decode_gqa.hip``: the MFMA decode attention for 5, 7 and 9..16 query heads
-per KV head; ``csrc/kernels/attn_extend.hip``: the MFMA kernel behind ``extend_attention``); CPU
+per KV head; ``csrc/kernels/attn_extend.hip`` and ``csrc/kernels/attn_extend_gqa.hip``: the MFMA
+kernels behind ``extend_attention``, for 1 / 2 / 4 / 8 and for 5, 7 and 9..16 heads per KV head); CPU
 tensors, other dtypes and shapes the kernels do not cover run the plain-torch
 definitions below (the fp32 oracle of the GPU tests).  These are inference ops: they
 record nothing on the tape and run under ``torch.no_grad()``.
@@ -303,7 +304,8 @@ def decode_attention(q, cache, layer: int, scale: float | None = None, num_split
     kernel; the result is bit-identical from run to run for a given ``num_splits``.  Ratios 1,
     2, 4 and 8 run the VALU kernel of ``attn_decode.hip``; 5, 7 and 9..16 the MFMA kernel of
     ``attn_decode_gqa.hip`` (both products on the matrix unit, P rounded to bf16 once), with the
-    same bit equalities between layouts and storage types; 3 and 6 take the reference.  A
+    same bit equalities between layouts and storage types; 3 and 6 take the reference.
+    ``extend_attention`` takes the same ratios.  A
     quantised cache runs the e4m3 instantiation of the same kernel (the bits of the bf16 one
     over ``cache.dequant(layer)``); elsewhere it is the reference over ``cache.dequant(layer)``."""
     B, Tq, Hq, D = q.shape
@@ -389,7 +391,7 @@ def default_extend_splits(batch: int, num_kv_heads: int, T: int, max_len: int) -
     return int(N.lib().pa_attn_extend_splits(int(batch), int(num_kv_heads), int(T), int(max_len)))
 
 
-def _extend_kernel(q, cache, layer, scale, num_splits, base_len, rows_t, out=None):
+def _extend_kernel(q, cache, layer, scale, num_splits, base_len, rows_t, out=None, entry="pa_attn_extend"):
     """Launch pa_attn_extend when it takes the problem; None otherwise.  ``out``: a contiguous
     [B, T, Hq, D] buffer to write (the tests border it with a sentinel)."""
     B, T, Hq, D = q.shape
@@ -402,16 +404,22 @@ def _extend_kernel(q, cache, layer, scale, num_splits, base_len, rows_t, out=Non
     ns = default_extend_splits(B, Hk, T, S_max) if num_splits is None else int(num_splits)
     qst = ctypes_long_array(_fa_strides(q))
     geom = (cache.block_size, cache.max_blocks, cache.num_blocks) if paged else (0, 0, 0)
-    if not N.lib().pa_attn_extend_ok(B, T, S_max, Hq, Hk, D, ns, qst, *geom):
+    if not getattr(N.lib(), entry + "_ok")(B, T, S_max, Hq, Hk, D, ns, qst, *geom):
         return None
     o = torch.empty(B, T, Hq, D, dtype=q.dtype, device=q.device) if out is None else out
     ws = torch.empty(B * T * Hq * ns * (D + 2), dtype=torch.float32, device=q.device) if ns > 1 else None
     ksc = cache.k_scale[layer] if cache.quantized else None
     vsc = cache.v_scale[layer] if cache.quantized else None
-    N.call("pa_attn_extend", N.ptr(q), qst, N.ptr(cache.k[layer]), N.ptr(cache.v[layer]), N.ptr(ksc), N.ptr(vsc),
+    N.call(entry, N.ptr(q), qst, N.ptr(cache.k[layer]), N.ptr(cache.v[layer]), N.ptr(ksc), N.ptr(vsc),
            N.ptr(cache.block_table) if paged else None, geom[1], geom[2], geom[0], N.ptr(rows_t), N.ptr(base_len),
            N.ptr(o), N.ptr(ws), B, cache.batch, T, S_max, Hq, Hk, D, float(scale), ns, N.stream())
     return o
+
+
+def _extend_gqa_kernel(q, cache, layer, scale, num_splits, base_len, rows_t, out=None):
+    """Launch pa_attn_extend_gqa (``csrc/kernels/attn_extend_gqa.hip``) whatever the routing of
+    ``pa_attn_extend`` says, for any ratio up to 16; None when ``pa_attn_extend_gqa_ok`` refuses."""
+    return _extend_kernel(q, cache, layer, scale, num_splits, base_len, rows_t, out, "pa_attn_extend_gqa")
 
 
 @torch.no_grad()
@@ -428,12 +436,14 @@ def extend_attention(q, cache, layer: int, scale: float | None = None, num_split
     row ``rows[i]``; inside ``cache.prefilling(rows)`` the mapping comes from the scope.  An
     explicit ``base_len`` is indexed by q row.
 
-    On the GPU (bf16 q, D in {64, 128}, Hq/Hk in {1, 2, 4, 8}: not the ratios 5, 7 and 9..16
-    that ``decode_attention`` also takes) this is ``pa_attn_extend`` of
-    ``csrc/kernels/attn_extend.hip``: both products on the bf16 MFMA, the key range cut into
-    ``num_splits`` ranges (``default_extend_splits``: from the launch shape only), bit-identical
-    from run to run.  The paged instantiation returns the bits of the contiguous one for equal
-    tokens, ``base_len`` and ``num_splits``; the e4m3 one the bits of the bf16 one over
+    On the GPU (bf16 q, D in {64, 128}, Hq/Hk in {1, 2, 4, 5, 7, 8, 9..16}: the ratios
+    ``decode_attention`` takes) this is ``pa_attn_extend``: both products on the bf16 MFMA, the
+    key range cut into ``num_splits`` ranges (``default_extend_splits``: from the launch shape
+    only), bit-identical from run to run.  Ratios 1, 2, 4 and 8 run the kernel of
+    ``csrc/kernels/attn_extend.hip``; 5, 7 and 9..16 the run-time-ratio kernel of
+    ``csrc/kernels/attn_extend_gqa.hip`` (the same tiles and arithmetic, rows of the 64-row
+    query tile that no whole token fills left dead); 3 and 6 take the reference.  The paged
+    instantiation returns the bits of the contiguous one for equal tokens, ``base_len`` and ``num_splits``; the e4m3 one the bits of the bf16 one over
     ``cache.dequant(layer)``.  At T = 1 it is *not* bit-equal to ``decode_attention`` (different
     arithmetic), and different chunkings of the same tokens are not bit-equal to each other.
     CPU tensors, other dtypes, other shapes and a misaligned q run the plain-torch reference
